@@ -28,9 +28,9 @@ Timing protocol (every rank):
      --steps K steps each (every job: one persistent launch from the same y0 +,
      for N > 1, the RCCL all-gather of the final states, which runs on RCCL's
      stream and overlaps the next job's kernel; every gather is complete before
-     the closing barrier); R = 1 when one job
-     lasts >= --min-timed-ms (default 40 ms), otherwise the smallest R that
-     fills it.  R is reported as "reps"; "ms_per_step" and "value" are means
+     the closing barrier); R = 1 by default, so that --steps is the number of
+     timed steps; with --min-timed-ms > 0, R is the smallest count whose jobs
+     fill that time.  R is reported as "reps"; "ms_per_step" and "value" are means
      over the R*K timed steps, "roofline.kernel_ms_per_launch" the HIP-event
      time over the R launches (one event pair on the launch stream around all of
      them) divided by their number; "roofline.frac_wall" the same fraction from
@@ -54,7 +54,10 @@ per sample).  With N > 1 the default shard is 8192 samples per GPU
 time and the isolated cost of the final gather.
 
 Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for the roofline and
-cpu_baseline definitions.
+cpu_baseline definitions.  With --dump-outputs DIR rank 0 also writes the final
+states the last timed job returned (with N > 1: the gathered ensemble) to
+DIR/final_states.npy; the inputs are seeded, so two builds can be compared
+output for output.
 """
 import argparse
 import glob
@@ -91,6 +94,8 @@ CONFIG_NAMES = ('kdv_n64_b4096', 'ks_n256_b8192', 'burgers_per_substep', 'burger
                 'adaptive_ks_n256_b8192', 'ks_n256_b1024', 'adaptive_rk23_b256', 'burgers_b512',
                 'weno_exact_n512_b2048', 'tower_f16_b4096')
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: total size of the written arrays
+
 
 def parse_args(argv=None):
   ap = argparse.ArgumentParser()
@@ -122,8 +127,9 @@ def parse_args(argv=None):
                   choices=['auto', 'mfma', 'mfma64', 'mfma64w32', 'mfma256', 'generic'])
   ap.add_argument('--preheat-ms', type=float, default=300.0,
                   help='run the timed kernel this long before --warmup (0 disables)')
-  ap.add_argument('--min-timed-ms', type=float, default=1000.0,
-                  help='repeat the K-step job until the timed region lasts this long')
+  ap.add_argument('--min-timed-ms', type=float, default=0.0,
+                  help='repeat the K-step job until the timed region lasts this long; 0 (the '
+                       'default): the timed region is exactly one job of --steps steps')
   ap.add_argument('--configs', default='all',
                   help="comma list of the extra measurements at --gpus 1 ('all', 'none', or of "
                        + ', '.join(CONFIG_NAMES) + ')')
@@ -144,7 +150,13 @@ def parse_args(argv=None):
                        'in config.library, never a headline run')
   ap.add_argument('--cpu-seconds', type=float, default=12.0,
                   help='budget for the CPU baseline sample (0 disables)')
+  ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                  help='after the timed region, write what its last job returned (the final '
+                       'states) as DIR/<name>.npy; at most {} MB in all, larger outputs as '
+                       'a fixed, seeded sample of their samples'.format(DUMP_LIMIT_BYTES >> 20))
   args = ap.parse_args(argv)
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be >= 1 and --warmup >= 0')
   if args.batch is None:
     args.batch = 4096 if args.gpus == 1 else 8192
   return args
@@ -493,9 +505,12 @@ def measure(args, model, y0_host, world, n, batch, sample_clocks=False):
     sys.stderr.write('bench.py: WARNING: the state is not finite after the timed run '
                      '(batch {}): its throughput is reported with "finite": false and '
                      'must not be quoted\n'.format(batch))
+  # what the last timed job returned: its final states, with N > 1 gathered over the ranks
+  last = (reps - 1) & 1
+  output = finals[last] if world == 1 else gathers[last].reshape(1, world * batch, n)
   return dict(wall=wall, kernel_ms=kernel_ms, reps=reps, finite=finite,
               preheat_ms=heated, preheat_launches=heat_launches, clocks=clocks,
-              per_rank=per_rank, solo=solo)
+              per_rank=per_rank, solo=solo, output=output)
 
 
 def summarize(args, eq, model, m, world, n, batch, stages):
@@ -578,6 +593,23 @@ def scaling_detail(args, m, world, n, batch, value):
       'note': 'rank 0 alone on its shard (others idle at a barrier), same steps x reps; '
               'efficiency = value / (n_gpus x n1_value)',
   }
+
+
+def dump_output(out_dir, name, array, limit=DUMP_LIMIT_BYTES):
+  """--dump-outputs: writes array [snapshots, samples, x] (float32 or float64) as
+  out_dir/<name>.npy.  Above `limit` bytes only a fixed, seeded subset of the samples
+  (axis 1, ascending) is written, the same one for every run of the same shape."""
+  if array.dtype not in (np.float32, np.float64):
+    raise TypeError('{}: dtype {} is neither float32 nor float64'.format(name, array.dtype))
+  if array.nbytes > limit:
+    samples = array.shape[1]
+    keep = max(1, samples * limit // array.nbytes)
+    rows = np.sort(np.random.RandomState(0).choice(samples, keep, replace=False))
+    array = array[:, rows]
+  os.makedirs(out_dir, exist_ok=True)
+  path = os.path.join(out_dir, name + '.npy')
+  np.save(path, np.ascontiguousarray(array))
+  return path
 
 
 def _variant(args, **overrides):
@@ -1101,6 +1133,10 @@ def main():
   n = eq.grid.solution_num_points
 
   m = measure(args, model, y0_host, world, n, batch, sample_clocks=(rank == 0))
+  output = m.pop('output')
+  if rank == 0 and args.dump_outputs:
+    dump_output(args.dump_outputs, 'final_states', output.cpu().numpy())
+  del output
   secondary = None
   if world == 1 and args.secondary_batch > 0 and args.secondary_batch != batch:
     b2 = args.secondary_batch

@@ -4,6 +4,9 @@ import importlib.util
 import json
 import os
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -48,8 +51,9 @@ def test_bench_defaults_match_baseline_config():
   assert (args.gpus, args.steps, args.batch, args.num_points, args.equation) == (
       1, 1000, 4096, 64, 'burgers')
   assert args.secondary_batch == 1024
-  # a timed region the driver's GPU-activity sampler can see
-  assert args.preheat_ms >= 200.0 and args.min_timed_ms >= 1000.0
+  # pre-heated clocks; the timed region is exactly --steps steps (one job, no repetitions)
+  assert args.preheat_ms >= 200.0 and args.min_timed_ms == 0.0
+  assert args.dump_outputs is None
   # the rest of the contract rides in the same run at N = 1
   assert args.configs == 'all' and set(bench.CONFIG_NAMES) >= {
       'kdv_n64_b4096', 'ks_n256_b8192', 'burgers_per_substep', 'burgers_per_step', 'stream_fixed',
@@ -59,3 +63,40 @@ def test_bench_defaults_match_baseline_config():
   assert bench.parse_args(['--gpus', '8', '--batch', '512']).batch == 512
   assert args.scheme == 'midpoint' and args.launch_mode == 'persistent'
   assert bench.PEAK_FP32_TFLOPS == 157.3 and bench.PEAK_HBM_GBPS == 8000.0
+
+
+def test_bench_rejects_step_counts_it_cannot_time():
+  bench = _bench()
+  for argv in (['--steps', '0'], ['--warmup', '-1']):
+    with pytest.raises(SystemExit):
+      bench.parse_args(argv)
+
+
+def test_dump_output_writes_small_arrays_whole(tmp_path):
+  bench = _bench()
+  for dtype in (np.float32, np.float64):
+    array = np.random.RandomState(1).standard_normal((1, 32, 64)).astype(dtype)
+    path = bench.dump_output(str(tmp_path / dtype.__name__), 'final_states', array)
+    assert path == str(tmp_path / dtype.__name__ / 'final_states.npy')
+    got = np.load(path)
+    assert got.dtype == dtype
+    np.testing.assert_array_equal(got, array)
+  with pytest.raises(TypeError):
+    bench.dump_output(str(tmp_path), 'ints', np.zeros((1, 4, 4), np.int32))
+
+
+def test_dump_output_samples_large_arrays_reproducibly(tmp_path):
+  """Above the limit: a seeded subset of the samples (axis 1), in order, within the
+  limit, and the same subset on every call for the same shape."""
+  bench = _bench()
+  samples, n = 1000, 16
+  array = np.arange(samples * n, dtype=np.float64).reshape(1, samples, n)
+  limit = 100 * n * 8 + 7          # room for 100 samples
+  first = np.load(bench.dump_output(str(tmp_path / 'a'), 'final_states', array, limit=limit))
+  second = np.load(bench.dump_output(str(tmp_path / 'b'), 'final_states', array, limit=limit))
+  assert first.shape == (1, 100, n) and first.nbytes <= limit
+  np.testing.assert_array_equal(first, second)
+  rows = first[0, :, 0] / n         # every kept row is a whole row of the input
+  assert (np.diff(rows) > 0).all() and rows.max() > samples / 2
+  np.testing.assert_array_equal(first[0], array[0, rows.astype(int)])
+  assert bench.DUMP_LIMIT_BYTES == 64 << 20

@@ -4,8 +4,10 @@ final states; the result must equal the single-process run of the whole
 ensemble bit for bit (samples are independent; scripts/run_evaluation.py:212-221,
 xarray_beam.py:127-154 is the reference's gather).
 
-  * backend "nccl" (RCCL, device tensors): needs two GPUs -- RCCL refuses two
-    ranks on one device -- and is skipped, loudly, on a one-GPU box;
+  * backend "nccl" (RCCL, device tensors): one GPU per rank on a box with two;
+    RCCL refuses two ranks on one device, so on a one-GPU box a single rank
+    runs both shards through the kernel and the RCCL all-gather of an RCCL
+    world of one;
   * backend "gloo": both ranks share cuda:0 for the kernel and gather the slabs
     through host memory; runs on any GPU box.
 """
@@ -64,15 +66,41 @@ def _worker(rank, world, port, backend, tmpdir):
     dist.destroy_process_group()
 
 
+def _one_gpu_nccl_worker(rank, port, tmpdir):
+  """The nccl case on a one-GPU box: both shards of the two-rank split through the
+  HIP kernel on cuda:0, their slabs all-gathered by RCCL on device tensors in a
+  world of one rank."""
+  os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK='0',
+                    WORLD_SIZE='1', LOCAL_RANK='0', HSA_ENABLE_IPC_MODE_LEGACY='0')
+  from ddd1d_amd import distributed
+  torch.cuda.set_device(0)
+  dist.init_process_group('nccl', rank=0, world_size=1, device_id=torch.device('cuda', 0))
+  try:
+    slabs = []
+    for shard in range(2):
+      lo, hi = distributed.shard_bounds(TOTAL, shard, 2)
+      model, y0 = _ensemble(lo, hi)
+      slabs.append(model.integrate_fixed(y0, STEPS, dt=1e-3, save_every=STEPS)[0])
+      assert model.kernel_name.startswith('mfma_f32')
+    local = torch.cat(slabs)
+    gathered = torch.empty_like(local)
+    dist.all_gather_into_tensor(gathered, local)                          # RCCL
+    torch.cuda.synchronize()
+    assert gathered.is_cuda
+    np.save(os.path.join(tmpdir, 'gathered.npy'), gathered.cpu().numpy())
+  finally:
+    dist.destroy_process_group()
+
+
 @pytest.mark.parametrize('backend', ['gloo', 'nccl'])
 def test_two_ranks_hip_kernel_and_gather(tmp_path, backend):
-  if backend == 'nccl' and torch.cuda.device_count() < 2:
-    pytest.skip('RCCL needs one GPU per rank; this box has {}'.format(
-        torch.cuda.device_count()))
   with socket.socket() as s:
     s.bind(('127.0.0.1', 0))
     port = s.getsockname()[1]
-  mp.spawn(_worker, args=(2, port, backend, str(tmp_path)), nprocs=2, join=True)
+  if backend == 'nccl' and torch.cuda.device_count() < 2:
+    mp.spawn(_one_gpu_nccl_worker, args=(port, str(tmp_path)), nprocs=1, join=True)
+  else:
+    mp.spawn(_worker, args=(2, port, backend, str(tmp_path)), nprocs=2, join=True)
   gathered = np.load(os.path.join(str(tmp_path), 'gathered.npy'))
   model, y0 = _ensemble(0, TOTAL)
   want = model.integrate_fixed(y0, STEPS, dt=1e-3, save_every=STEPS)[0].cpu().numpy()
@@ -105,16 +133,17 @@ def test_bench_two_ranks_on_this_box():
   assert result['configs'] is None
 
 
-def test_bench_eight_ranks_on_this_box():
-  """The command shape of the first 8-GPU run -- `bench.py --gpus 8`, self-launched
-  under torch.distributed.run -- with eight ranks sharing cuda:0 over gloo: the
-  8-rank rendezvous, the agreed repetition count, per-rank tables of length 8 and
-  the gathered ensemble, which must equal the single-process run of the same 512
-  global sample ids bit for bit."""
+def test_bench_four_ranks_on_this_box():
+  """The command shape of a multi-GPU run -- `bench.py --gpus N`, self-launched under
+  torch.distributed.run -- with four ranks sharing cuda:0 over gloo: the N-rank
+  rendezvous, the agreed repetition count, per-rank tables of length N and the
+  gathered ensemble, which must equal the single-process run of the same 256 global
+  sample ids bit for bit.  Four ranks and this process keep the GPU open in at most
+  five processes at once."""
   import hashlib
   env = {k: v for k, v in os.environ.items()
          if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-  out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8',
+  out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '4',
                         '--backend', 'gloo', '--batch', '64', '--steps', '5', '--warmup', '2',
                         '--preheat-ms', '10', '--min-timed-ms', '5', '--configs', 'none',
                         '--cpu-seconds', '0'], env=env, capture_output=True, text=True,
@@ -122,22 +151,22 @@ def test_bench_eight_ranks_on_this_box():
   assert out.returncode == 0, out.stderr[-3000:]
   line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]
   result = json.loads(line)
-  assert result['n_gpus'] == 8 and result['config']['global_batch'] == 512
+  assert result['n_gpus'] == 4 and result['config']['global_batch'] == 256
   assert result['config']['visible_devices'] == torch.cuda.device_count()
   assert result['config']['finite'] and result['value'] > 0 and result['scaling'] == 'weak'
   per_rank = result['per_rank']
   for key in ('wall_ms', 'kernel_ms', 'gather_ms_isolated'):
-    assert len(per_rank[key]) == 8 and all(v > 0 for v in per_rank[key]), key
-  assert per_rank['gathered_shape'] == [512, 64]
+    assert len(per_rank[key]) == 4 and all(v > 0 for v in per_rank[key]), key
+  assert per_rank['gathered_shape'] == [256, 64]
   # the 1 -> N point measured in the same invocation: rank 0 alone on its shard
   detail = result['scaling_detail']
-  assert detail['nranks'] == 8 and detail['backend'] == 'gloo' and detail['n1_batch'] == 64
+  assert detail['nranks'] == 4 and detail['backend'] == 'gloo' and detail['n1_batch'] == 64
   assert detail['n1_value'] > 0 and detail['n1_ms_per_step'] > 0
-  assert abs(detail['efficiency'] - result['value'] / (8 * detail['n1_value'])) < 1e-9
-  # the single-process run of global sample ids 0 .. 511 (rank r owns [64 r, 64 r + 64))
+  assert abs(detail['efficiency'] - result['value'] / (4 * detail['n1_value'])) < 1e-9
+  # the single-process run of global sample ids 0 .. 255 (rank r owns [64 r, 64 r + 64))
   import bench
-  args = bench.parse_args(['--batch', '512', '--steps', '5'])
-  eq, model, _, y0 = bench.build_workload(args, 0, 512)
+  args = bench.parse_args(['--batch', '256', '--steps', '5'])
+  eq, model, _, y0 = bench.build_workload(args, 0, 256)
   want = model.integrate_fixed(y0, 5, dt=eq.time_step, scheme='midpoint', save_every=5)[0]
   assert per_rank['gathered_sha1'] == hashlib.sha1(want.cpu().numpy().tobytes()).hexdigest()
 
@@ -189,19 +218,21 @@ print('RCCL_ONE_RANK_OK')
 
 def test_bench_self_launches_its_ranks():
   """`python bench.py --gpus 2` without a torchrun environment starts its own
-  ranks (bench.py: relaunch_under_torchrun) and prints one JSON line."""
-  if torch.cuda.device_count() < 2:
-    pytest.skip('needs two GPUs; this box has {}'.format(torch.cuda.device_count()))
+  ranks (bench.py: relaunch_under_torchrun) and prints one JSON line: over RCCL,
+  one GPU per rank, where the box has two GPUs; over gloo, both ranks on cuda:0,
+  where it has one (RCCL refuses two ranks on one device)."""
+  backend = 'nccl' if torch.cuda.device_count() >= 2 else 'gloo'
   env = {k: v for k, v in os.environ.items()
          if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
   out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
                         '--steps', '20', '--warmup', '5', '--batch', '2048',
-                        '--cpu-seconds', '0'], env=env, capture_output=True, text=True,
-                       timeout=900)
+                        '--backend', backend, '--cpu-seconds', '0'], env=env,
+                       capture_output=True, text=True, timeout=900)
   assert out.returncode == 0, out.stderr[-2000:]
   line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]
   result = json.loads(line)
   assert result['n_gpus'] == 2 and result['config']['global_batch'] == 4096
+  assert result['config']['backend'] == backend
   assert result['config']['finite'] and result['value'] > 0
 
 
