@@ -269,6 +269,31 @@ void ring_parker(Ring* rg) {
   }
 }
 
+// Geometry of the MFMA path.  rows: grid points per workgroup; wave_rows: per
+// wavefront.  One free-running 64-row wavefront per workgroup when whole
+// samples fit 64 rows (optionally split over two 32-row or four 16-row wavefronts),
+// else 256 rows on four wavefronts with block barriers.
+struct MfmaGeometry { int rows, wave_rows; };
+
+// Which kernel a call runs (plan_launch): decided once per launch from the model, the
+// operation and a few facts of the call's arguments, then launched as planned.  The model
+// keeps the plan of its most recent launch (ddd_kernel_name).
+enum class Op { substep, step, persistent, adaptive, ring };
+enum class Route { spectral, stream_fixed, lean, weno, generic, mfma };
+// 64-row MFMA groups on one, two (kSplit) or four (kQuad) wavefronts, or one wavefront on the
+// 16-channel tiles of nets of up to 16 filters (HalfTower / Tile16Tower)
+enum class Tile { one_wave, split, quad, half };
+
+struct Plan {
+  Op op = Op::substep;
+  Route route = Route::generic;
+  MfmaGeometry geo{64, 64};
+  int eq = -1;                  // per-equation kernel id, or -1
+  Tile tile = Tile::one_wave;
+  bool traced = false;          // (probes) the phase-traced persistent integrator
+  const char* name = nullptr;   // ddd_kernel_name; nullptr: no launch recorded
+};
+
 }  // namespace
 
 struct ddd_model {
@@ -280,11 +305,7 @@ struct ddd_model {
   int force_rows = 0;                // 0 = automatic; 64 / 32 (64 rows on two waves) / 256
   bool explicit_kernel = false;      // ddd_set_kernel chose a family (disables automatic variants)
   bool spec_folded = false;          // w_final4 (specialised kernels) holds the folded output layer
-  bool last_launch_streamed = false; // the most recent launch was the streaming fixed-stencil kernel
-  bool last_launch_split = false;    // ... the persistent integrator with two 32-row wavefronts per sample
-  bool last_launch_lean = false;     // ... the lane == grid point kernel of rhs_lean.h
-  bool last_launch_quad = false;     // ... four 16-row wavefronts per group (rhs_mfma.h kQuad)
-  int last_batch = 0;                // batch of the most recent launch (kernel_name)
+  Plan last_plan;                    // the most recent launch (cleared by ddd_set_kernel)
   int64_t fma_per_point = 0;
   // device allocations
   float* d_weights = nullptr;
@@ -300,9 +321,7 @@ struct ddd_model {
   float* d_w_hidden_half = nullptr;   // block-diagonal packing of a <= 16-filter net (rhs_mfma.h HalfTower)
   float* d_w_final4_half = nullptr;
   float* d_w_t16 = nullptr;           // the same net as 16x16x4 A operands (rhs_mfma.h Tile16Tower)
-  bool last_launch_half = false;
   bool wide = false;                 // run-time kernels of the wide flavour (rhs_mfma.h kWide)
-  bool split_auto = true;            // small ensembles: two 32-row wavefronts per sample (kSplit)
   int tower_k = 5, tower_cb = 1;     // conv tower the MFMA kernels carry the net in (rhs_mfma.h Tower)
   bool big() const { return tower_k != ddd::mfma::kKW || tower_cb != 1; }
   float4* d_frc = nullptr;
@@ -981,12 +1000,6 @@ int check_batch(const ddd_model* m, int batch, bool want_spectral = false) {
   return DDD_OK;
 }
 
-// Geometry of the MFMA path.  rows: grid points per workgroup; wave_rows: per
-// wavefront.  One free-running 64-row wavefront per workgroup when whole
-// samples fit 64 rows (optionally split over two 32-row wavefronts), else 256
-// rows on four wavefronts with block barriers.
-struct MfmaGeometry { int rows, wave_rows; };
-
 // One-time hardware check of the DPP wavefront rotate the one-wave kernel uses
 // for the flux exchange when N = 64 (falls back to ds_bpermute otherwise).
 int dpp_wave_rol_ok() {
@@ -1018,17 +1031,25 @@ int device_simds() {
   return simds;
 }
 
-MfmaGeometry mfma_geometry(const ddd_model* m, int batch) {
+MfmaGeometry mfma_geometry(const ddd_model* m) {
   const bool fits64 = m->dp.N <= 64 && 64 % m->dp.N == 0;
   if (m->force_rows == 256 || !fits64) return {256, 64};
   if (m->force_rows == 64) return {64, 64};
   if (m->force_rows == 32 && !m->wide && !m->big()) return {64, 32};   // (no wide / other-tower split)
-  if (m->force_rows == 16 && !m->wide && !m->big()) return {64, 16};   // (launch_integrate alone honours it)
-  // Two 32-row wavefronts per sample are never the geometry of the fused substep or
-  // the adaptive kernels; launch_integrate alone switches small float32 ensembles to
-  // the split integrators (rhs_mfma.h kSplit), where the measurement says it pays.
-  (void)batch;
+  if (m->force_rows == 16 && !m->wide && !m->big()) return {64, 16};
   return {64, 64};
+}
+
+// Workgroups of `batch` samples in geometry geo ...
+int group_count(const ddd_model* m, MfmaGeometry geo, int batch) {
+  const int spg = geo.rows / m->dp.N;
+  return (batch + spg - 1) / spg;
+}
+
+// ... and how many of them the machine holds resident (the grid of the kernels that walk
+// over several groups: substep_multi_kernel, step_multi_kernel, the command ring).
+int resident_groups(MfmaGeometry geo) {
+  return geo.rows == 64 ? 2 * device_simds() : device_simds() / 2;
 }
 
 // Equation id of the compile-time specialised integrator this model can use,
@@ -1067,15 +1088,6 @@ bool aligned16(const void* ptr) {
   return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0;
 }
 
-// Fixed-stencil models without forcing: the streaming kernel (rhs_stream.h).
-bool use_stream_kernel(const ddd_model* m, const ddd::SubstepArgs& a) {
-  if (!ddd::stream::supports(m->dp) || m->explicit_kernel) return false;
-  if (a.derivs_out != nullptr || a.coeffs_out != nullptr) return false;
-  if (g_debug.no_stream) return false;
-  return aligned16(a.y_in) && aligned16(a.y_base) && aligned16(a.y_out) &&
-         aligned16(a.acc_in) && aligned16(a.acc_out);
-}
-
 // WENO5 + Godunov-flux models (integrate.WENODifferentiator, the exact Burgers solver) on
 // the one-wavefront-per-sample kernels of rhs_weno.h; an explicit ddd_set_kernel(GENERIC)
 // keeps the generic kernel (A/B, and the grids rhs_weno.h does not carry).
@@ -1084,14 +1096,239 @@ bool use_weno_kernel(const ddd_model* m) {
          ddd::weno::supports(m->dp);
 }
 
+// The persistent kernels of fixed-stencil models and one-layer nets (rhs_lean.h) built, one
+// per taps x derivatives: f(taps, derivatives) as integral constants for dp's; false when
+// there is none (other tap counts: the MFMA-path kernels with the tower skipped).
+template <int kK, int kD, typename F>
+bool lean_kernel_if(int taps, int derivs, F& f) {
+  if (taps != kK || derivs != kD) return false;
+  f(std::integral_constant<int, kK>{}, std::integral_constant<int, kD>{});
+  return true;
+}
+template <typename F>
+bool with_lean_kernel(const ddd::DevParams& dp, F&& f) {
+  if (!ddd::lean::supports(dp)) return false;
+  const int t = dp.fixed ? 0 : dp.linear_taps, d = dp.D;
+  return lean_kernel_if<0, 1>(t, d, f) || lean_kernel_if<0, 2>(t, d, f) ||
+         lean_kernel_if<0, 3>(t, d, f) || lean_kernel_if<0, 4>(t, d, f) ||
+         lean_kernel_if<3, 1>(t, d, f) || lean_kernel_if<3, 2>(t, d, f) ||
+         lean_kernel_if<3, 3>(t, d, f) || lean_kernel_if<5, 1>(t, d, f) ||
+         lean_kernel_if<5, 2>(t, d, f) || lean_kernel_if<5, 3>(t, d, f) ||
+         lean_kernel_if<7, 1>(t, d, f) || lean_kernel_if<7, 2>(t, d, f);
+}
+
+// f(EQ) as an integral constant: the launch.h templates of the per-equation kernels.
+template <typename F>
+void with_equation(int eq, F&& f) {
+  switch (eq) {
+    case ddd::EQ_BURGERS: f(std::integral_constant<int, ddd::EQ_BURGERS>{}); break;
+    case ddd::EQ_BURGERS_CONS: f(std::integral_constant<int, ddd::EQ_BURGERS_CONS>{}); break;
+    case ddd::EQ_KDV: f(std::integral_constant<int, ddd::EQ_KDV>{}); break;
+    case ddd::EQ_KDV_CONS: f(std::integral_constant<int, ddd::EQ_KDV_CONS>{}); break;
+    case ddd::EQ_KS: f(std::integral_constant<int, ddd::EQ_KS>{}); break;
+    case ddd::EQ_KS_CONS: f(std::integral_constant<int, ddd::EQ_KS_CONS>{}); break;
+    default: break;
+  }
+}
+
+template <typename F>
+void with_rows(int rows, F&& f) {
+  if (rows == 64) f(std::integral_constant<int, 64>{});
+  else f(std::integral_constant<int, 256>{});
+}
+
+// f(taps, 32-channel blocks, rows) as integral constants for the model's tower other than
+// 5 taps x 32 channels (launch.h: DDD_FOR_EACH_BIG_TOWER).
+template <typename F>
+void with_big_tower(const ddd_model* m, int rows, F&& f) {
+#define DDD_BIG_TOWER(K, CB)                                                     \
+  if (m->tower_k == K && m->tower_cb == CB)                                      \
+    with_rows(rows, [&](auto r) {                                                \
+      f(std::integral_constant<int, K>{}, std::integral_constant<int, CB>{}, r); \
+    });
+  DDD_FOR_EACH_BIG_TOWER(DDD_BIG_TOWER)
+#undef DDD_BIG_TOWER
+}
+
+const char* plan_name(const Plan& p) {
+  switch (p.route) {
+    case Route::spectral: return "spectral_f64";
+    case Route::stream_fixed: return "stream_fixed";
+    case Route::lean: return "valu_f32_lean";
+    case Route::weno: return "valu_f32_weno";
+    case Route::generic: return "generic";
+    case Route::mfma: break;
+  }
+  if (p.geo.rows == 256) return "mfma_f32_r256";
+  switch (p.tile) {
+    case Tile::quad: return "mfma_f32_r64w16";
+    case Tile::half: return "mfma_f32_r64h16";
+    case Tile::split: return "mfma_f32_r64w32";
+    default: return "mfma_f32_r64";
+  }
+}
+
+// What the rules read of a call's arguments.
+struct CallFacts {
+  int batch = 0;
+  bool f64 = false;       // float64 state
+  bool views = false;     // derivative or coefficient views requested
+  bool coeffs = false;    // ... coefficients (the WENO kernels write none)
+  bool aligned = false;   // every state array 16-byte aligned (the streaming kernels)
+};
+
+CallFacts substep_facts(const ddd::SubstepArgs& a) {
+  return {a.batch, false, a.derivs_out != nullptr || a.coeffs_out != nullptr, a.coeffs_out != nullptr,
+          aligned16(a.y_in) && aligned16(a.y_base) && aligned16(a.y_out) &&
+              aligned16(a.acc_in) && aligned16(a.acc_out)};
+}
+
+// Geometry, per-equation kernel and tile of an MFMA launch.
+void plan_mfma(const ddd_model* m, const CallFacts& f, Plan* p) {
+  const bool automatic = !m->explicit_kernel;
+  MfmaGeometry geo = mfma_geometry(m);
+  int eq = -1;
+  switch (p->op) {
+    case Op::substep:
+    case Op::ring:
+      if (geo.wave_rows == 16) geo = {64, 64};   // (four-wavefront groups: integrators only)
+      // per-equation instantiations for the plain substep (no derivative views)
+      if (!f.views && geo.wave_rows == 64) eq = spec_equation(m, geo.rows);
+      break;
+    case Op::step:
+      if (automatic) eq = spec_equation(m, geo.rows);
+      break;
+    case Op::persistent:
+      if (geo.rows == 64 && geo.wave_rows == 64 && !f.f64 && automatic &&
+          m->dp.w_final4_split != nullptr && spec_equation(m, 64) >= 0) {
+        // small ensembles: two 32-row wavefronts per sample (rhs_mfma.h kSplit)
+        // measured (profiles/r4_ablation.txt, N = 64): B = 256: 1.63 x the one-wavefront kernel (twice
+        // the SIMDs busy), B = 512: 0.97 x, B = 1024: 0.89 x (two coupled wavefronts per SIMD lose to one
+        // free-running one) -- so only below three eighths of a wavefront per SIMD
+        const int groups = group_count(m, geo, f.batch);
+        if (8 * groups <= 3 * device_simds()) geo = {64, 32};
+        // ... and FOUR 16-row wavefronts per group (kQuad: every layer on 16x16x4 MFMAs, one
+        // group on the four SIMDs of a CU) while that leaves at most two wavefronts per SIMD
+        // (measured, profiles/r6_ablation.txt)
+        if (m->dp.w_quad != nullptr && 2 * groups <= device_simds()) geo = {64, 16};
+      }
+      // an explicit DDD_KERNEL_MFMA_ROWS64_W16 where the model has no such kernel (float64
+      // state, no per-equation specialisation): the one-wavefront geometry
+      if (geo.wave_rows == 16 && !(!f.f64 && m->dp.w_quad != nullptr && spec_equation(m, 64) >= 0))
+        geo = {64, 64};
+      // per-equation instantiations: 64-row wavefronts in both geometries and both state types,
+      // the split and quad groups for float32 state
+      if (geo.wave_rows != 32 || (!f.f64 && m->dp.w_final4_split != nullptr))
+        eq = spec_equation(m, geo.rows);
+#ifdef DDD_PROBES
+      if (g_debug.trace_ptr != 0) {
+        // phase tracing: the dedicated traced instantiation (headline config) or
+        // the run-time-parameterised kernel
+        p->traced = eq == ddd::EQ_BURGERS_CONS && geo.rows == 64 && !f.f64;
+        if (!p->traced) eq = -1;
+      }
+#endif
+      break;
+    case Op::adaptive: {
+      // the two-wave split has no adaptive instantiation.  Small ensembles: every 64-row group
+      // on four 16-row wavefronts (rhs_mfma.h kQuad), as for the fixed-step integrators --
+      // the reference's callers integrate tens to hundreds of samples
+      // (scripts/run_evaluation.py:212-221)
+      const bool want_quad = geo.rows == 64 &&
+                             (geo.wave_rows == 16 || (geo.wave_rows == 64 && m->force_rows == 0));
+      if (geo.wave_rows != 64) geo = {64, 64};
+      eq = spec_equation(m, geo.rows);
+      if (want_quad && m->dp.w_quad != nullptr && eq >= 0 &&
+          (m->force_rows == 16 ||
+           (automatic && 2 * group_count(m, geo, f.batch) <= device_simds())))
+        geo = {64, 16};
+      break;
+    }
+  }
+  p->geo = geo;
+  p->eq = eq;
+  p->tile = geo.wave_rows == 32 ? Tile::split : geo.wave_rows == 16 ? Tile::quad : Tile::one_wave;
+  // nets of up to 16 filters: the 16-channel tiles of the per-equation one-wave kernels
+  if (p->tile == Tile::one_wave && geo.rows == 64 && eq >= 0 && !p->traced &&
+      m->d_w_hidden_half != nullptr && m->d_w_final4_half != nullptr && m->d_w_t16 != nullptr &&
+      !g_debug.no_half)
+    p->tile = Tile::half;
+}
+
+// The one place that chooses a launch's kernel.  Order: spectral, the streaming
+// fixed-stencil kernels, the lean kernel (persistent float32 integrator), MFMA, WENO,
+// generic.  Op::step plans a kernel that takes all stages of a step; without one the
+// plan's op is Op::substep (one launch per substep, each planned on its own).  Op::ring
+// plans the command ring's persistent kernel; when the call cannot ride the ring, the plan
+// is the one of Op::substep.
+Plan plan_launch(const ddd_model* m, Op op, const CallFacts& f) {
+  Plan p;
+  p.op = op;
+  const bool automatic = !m->explicit_kernel;
+  if (op == Op::ring) {
+    // per-equation kernels on one-wave groups (N | 64), the whole ensemble from sample 0, no
+    // derivative / coefficient views; opt-in (measured equal to the launches)
+    p = plan_launch(m, Op::substep, f);
+    if (m->region_mode == DDD_REGION_RING && automatic && f.batch > 0 &&
+        p.route == Route::mfma && p.geo.rows == 64 && p.eq >= 0) {
+      p.op = Op::ring;
+      p.tile = Tile::one_wave;   // (the ring kernel carries the net on the 32-channel tower)
+      p.name = plan_name(p);
+    }
+    return p;
+  }
+  if (m->spectral) {
+    p.route = Route::spectral;
+  } else if (automatic && !g_debug.no_stream && f.aligned && !f.views &&
+             (op == Op::substep ? ddd::stream::supports(m->dp)
+                                : op == Op::step && ddd::stream::step_supports(m->dp))) {
+    // fixed-stencil models without forcing: the streaming kernels (rhs_stream.h)
+    p.route = Route::stream_fixed;
+  } else if (m->kernel == DDD_KERNEL_MFMA) {
+    // fixed stencils / one-layer nets, float32 state, whole samples per wavefront: the
+    // lane == grid point kernel (no matrix work to schedule around)
+    if (op == Op::persistent && !f.f64 && automatic && !g_debug.no_lean &&
+        with_lean_kernel(m->dp, [](auto, auto) {})) {
+      p.route = Route::lean;
+    } else {
+      p.route = Route::mfma;
+      plan_mfma(m, f, &p);
+    }
+  } else if (use_weno_kernel(m) && !f.coeffs) {
+    p.route = Route::weno;
+  }
+  if (op == Op::step && p.route != Route::stream_fixed && !(p.route == Route::mfma && p.eq >= 0))
+    p.op = Op::substep;
+  p.name = plan_name(p);
+  return p;
+}
+
+// The parameters of one launch: the model's, with the forcing rows of its sample slab
+// (sample0: first sample of the launch in the model's per-sample tables) and the weights
+// of its tile.
+ddd::DevParams launch_params(ddd_model* m, const Plan& p, int sample0 = 0) {
+  if (p.route == Route::mfma) m->dp.dpp_rol = dpp_wave_rol_ok();
+  ddd::DevParams dp = m->dp;
+  if (sample0 != 0 && dp.forced) {
+    dp.frc += (size_t)sample0 * dp.P;
+    dp.runs += (size_t)sample0 * 8;
+  }
+  if (p.tile == Tile::half) {
+    dp.w_hidden = m->d_w_hidden_half;
+    dp.w_final4 = m->d_w_final4_half;
+    dp.w_quad = m->d_w_t16;
+  }
+  return dp;
+}
+
 // sample0: index of a.y_in's first sample in the model's per-sample tables (a
 // half-ensemble launch); grid_share: this launch may occupy 1 / grid_share of
 // the machine-sized grid (it runs next to grid_share - 1 others).
-int launch_substep(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream, int sample0 = 0,
-                   int grid_share = 1) {
+int launch_substep(ddd_model* m, const Plan& p, const ddd::SubstepArgs& a, hipStream_t stream,
+                   int sample0 = 0, int grid_share = 1) {
   if (a.batch == 0) return DDD_OK;
-  m->last_batch = a.batch;
-  if (use_stream_kernel(m, a)) {
+  m->last_plan = p;
+  if (p.route == Route::stream_fixed) {
     const long pts = (long)ddd::stream::samples_per_block(m->dp.N) * m->dp.N;
     const long total = (long)a.batch * m->dp.N;
     const unsigned blocks = (unsigned)((total + pts - 1) / pts);
@@ -1101,71 +1338,33 @@ int launch_substep(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream, 
     else
       hipLaunchKernelGGL(ddd::stream::fixed_substep_kernel<1>, dim3(blocks),
                          dim3(ddd::stream::kThreads), 0, stream, m->dp, a);
-    m->last_launch_streamed = true; m->last_launch_lean = false;
-    DDD_HIP(hipGetLastError());
-    return DDD_OK;
-  }
-  m->last_launch_streamed = false; m->last_launch_lean = false;
-  m->last_launch_split = false; m->last_launch_quad = false; m->last_launch_half = false;
-  if (m->kernel == DDD_KERNEL_MFMA) {
-    m->dp.dpp_rol = dpp_wave_rol_ok();
-    ddd::DevParams dp = m->dp;
-    if (sample0 != 0 && dp.forced) {   // per-sample forcing rows of this slab
-      dp.frc += (size_t)sample0 * dp.P;
-      dp.runs += (size_t)sample0 * 8;
-    }
-    MfmaGeometry geo = mfma_geometry(m, a.batch);
-    if (geo.wave_rows == 16) geo = {64, 64};   // (four-wavefront groups: persistent integrators only)
-    const int spg = geo.rows / m->dp.N;
-    const int blocks = (a.batch + spg - 1) / spg;
-    // per-equation instantiations for the plain substep (no derivative views)
-    const int eq = (a.derivs_out == nullptr && a.coeffs_out == nullptr && geo.wave_rows == 64)
-                       ? spec_equation(m, geo.rows) : -1;
+  } else if (p.route == Route::mfma) {
+    const ddd::DevParams dp = launch_params(m, p, sample0);
+    const int blocks = group_count(m, p.geo, a.batch);
     // specialised models: machine-sized grid, weights resident per wavefront,
     // each group walks over several row groups (substep_multi_kernel)
-    const int grid = std::min(blocks, (geo.rows == 64 ? 2 * device_simds() : device_simds() / 2) /
-                                          std::max(grid_share, 1));
-    // nets of up to 16 filters: 16-channel tiles (one-wave groups)
-    const bool half = eq >= 0 && geo.rows == 64 && m->d_w_hidden_half != nullptr &&
-                      m->d_w_final4_half != nullptr && m->d_w_t16 != nullptr && !g_debug.no_half;
-    m->last_launch_half = half;
-    if (half) { dp.w_hidden = m->d_w_hidden_half; dp.w_final4 = m->d_w_final4_half; dp.w_quad = m->d_w_t16; }
-#define DDD_SUBSTEP_CASE(EQ) \
-    case EQ:                                                                           \
-      if (half) ddd::launch::substep_half_spec<EQ>(dp, a, blocks, grid, stream);       \
-      else ddd::launch::substep_spec<EQ>(geo.rows, dp, a, blocks, grid, stream);       \
-      break;
-    switch (eq) {
-      DDD_SUBSTEP_CASE(ddd::EQ_BURGERS)
-      DDD_SUBSTEP_CASE(ddd::EQ_BURGERS_CONS)
-      DDD_SUBSTEP_CASE(ddd::EQ_KDV)
-      DDD_SUBSTEP_CASE(ddd::EQ_KDV_CONS)
-      DDD_SUBSTEP_CASE(ddd::EQ_KS)
-      DDD_SUBSTEP_CASE(ddd::EQ_KS_CONS)
-      default:
-        if (m->big()) {
-#define DDD_BIG_SUBSTEP(K, CB)                                                          \
-          if (m->tower_k == K && m->tower_cb == CB) {                                   \
-            if (geo.rows == 64) ddd::launch::substep_big_unit<K, CB, 64>(dp, a, blocks, stream); \
-            else ddd::launch::substep_big_unit<K, CB, 256>(dp, a, blocks, stream);      \
-          }
-          DDD_FOR_EACH_BIG_TOWER(DDD_BIG_SUBSTEP)
-#undef DDD_BIG_SUBSTEP
-        } else if (m->wide) {
-          if (geo.rows == 64) ddd::launch::substep_wide_unit<64>(dp, a, blocks, stream);
-          else ddd::launch::substep_wide_unit<256>(dp, a, blocks, stream);
-        } else {
-          ddd::launch::substep_runtime(geo.rows, geo.wave_rows, dp, a, blocks, stream);
-        }
+    const int grid = std::min(blocks, resident_groups(p.geo) / std::max(grid_share, 1));
+    if (p.eq >= 0) {
+      with_equation(p.eq, [&](auto eq) {
+        if (p.tile == Tile::half)
+          ddd::launch::substep_half_spec<decltype(eq)::value>(dp, a, blocks, grid, stream);
+        else
+          ddd::launch::substep_spec<decltype(eq)::value>(p.geo.rows, dp, a, blocks, grid, stream);
+      });
+    } else if (m->big()) {
+      with_big_tower(m, p.geo.rows, [&](auto k, auto cb, auto rows) {
+        ddd::launch::substep_big_unit<decltype(k)::value, decltype(cb)::value, decltype(rows)::value>(
+            dp, a, blocks, stream);
+      });
+    } else if (m->wide) {
+      with_rows(p.geo.rows, [&](auto rows) {
+        ddd::launch::substep_wide_unit<decltype(rows)::value>(dp, a, blocks, stream);
+      });
+    } else {
+      ddd::launch::substep_runtime(p.geo.rows, p.geo.wave_rows, dp, a, blocks, stream);
     }
-#undef DDD_SUBSTEP_CASE
-  } else if (use_weno_kernel(m) && a.coeffs_out == nullptr) {
-    ddd::DevParams dp = m->dp;
-    if (sample0 != 0 && dp.forced) {   // per-sample forcing rows of this slab
-      dp.frc += (size_t)sample0 * dp.P;
-      dp.runs += (size_t)sample0 * 8;
-    }
-    ddd::launch::weno_substep(dp, a, stream);
+  } else if (p.route == Route::weno) {
+    ddd::launch::weno_substep(launch_params(m, p, sample0), a, stream);
   } else {
     int rc = check_generic_lds(m, 0);
     if (rc) return rc;
@@ -1179,150 +1378,63 @@ int launch_substep(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream, 
   return DDD_OK;
 }
 
-template <int kRows, int kWR, typename ST>
-void launch_mfma_integrate(ddd_model* m, const ddd::IntegrateArgs& a, hipStream_t stream) {
-  m->dp.dpp_rol = dpp_wave_rol_ok();
-  const int spg = kRows / m->dp.N;
-  const int blocks = (a.batch + spg - 1) / spg;
-  const bool hoist = !m->dp.fixed && m->dp.L == 3;
-  constexpr bool f64 = std::is_same<ST, double>::value;
-  // per-equation instantiations exist for 64-row wavefronts: float32 state in
-  // both geometries, float64 state -- the SciPy-driven reference semantics,
-  // integrate.py:154 -- in the one-wave geometry (launch.h)
-  int eq = kWR == 64 ? spec_equation(m, kRows) : -1;   // (float64 state: both geometries since round 6)
-  if (kWR == 32 && !f64 && m->dp.w_final4_split != nullptr) eq = spec_equation(m, kRows);
-  if (kWR == 16) eq = (!f64 && m->dp.w_quad != nullptr) ? spec_equation(m, kRows) : -1;
-  bool traced = false;
-#ifdef DDD_PROBES
-  if (a.trace != nullptr) {
-    // phase tracing: the dedicated traced instantiation (headline config) or
-    // the run-time-parameterised kernel
-    traced = eq == ddd::EQ_BURGERS_CONS && kRows == 64 && !f64;
-    if (!traced) eq = -1;
-  }
-#endif
-  // nets of up to 16 filters: the block-diagonal tower (float32 state, one-wave groups)
-  const bool half = kRows == 64 && kWR == 64 && !traced && eq >= 0 &&
-                    m->d_w_hidden_half != nullptr && m->d_w_final4_half != nullptr && !g_debug.no_half;
-  m->last_launch_half = half;
-  ddd::DevParams dp_half = m->dp;
-  if (half) { dp_half.w_hidden = m->d_w_hidden_half; dp_half.w_final4 = m->d_w_final4_half; dp_half.w_quad = m->d_w_t16; }
-#define DDD_SPEC_CASE(EQ)                                                              \
-  case EQ:                                                                             \
-    if (half && f64) ddd::launch::integrate_half_f64_spec<EQ>(dp_half, a, blocks, stream); \
-    else if (half) ddd::launch::integrate_half_spec<EQ>(dp_half, a, blocks, stream);   \
-    else if (kWR == 16) ddd::launch::integrate_quad_spec<EQ>(m->dp, a, blocks, stream);     \
-    else if (kWR == 32) ddd::launch::integrate_split_spec<EQ>(m->dp, a, blocks, stream); \
-    else ddd::launch::integrate_spec<EQ>(kRows, f64, traced, m->dp, a, blocks, stream); \
-    return;
-  switch (eq) {
-    DDD_SPEC_CASE(ddd::EQ_BURGERS)
-    DDD_SPEC_CASE(ddd::EQ_BURGERS_CONS)
-    DDD_SPEC_CASE(ddd::EQ_KDV)
-    DDD_SPEC_CASE(ddd::EQ_KDV_CONS)
-    DDD_SPEC_CASE(ddd::EQ_KS)
-    DDD_SPEC_CASE(ddd::EQ_KS_CONS)
-    default: break;
-  }
-#undef DDD_SPEC_CASE
-  if (m->big()) {
-    if constexpr (kWR == 64) {
-#define DDD_BIG_INTEGRATE(K, CB)                                                         \
-      if (m->tower_k == K && m->tower_cb == CB)                                          \
-        ddd::launch::integrate_big_unit<K, CB, kRows, f64>(m->dp, a, blocks, stream);
-      DDD_FOR_EACH_BIG_TOWER(DDD_BIG_INTEGRATE)
-#undef DDD_BIG_INTEGRATE
-    }
-    return;
-  }
-  if (m->wide) {
-    if (kWR == 64) ddd::launch::integrate_wide_unit<kRows, f64 ? 1 : 0>(hoist, m->dp, a, blocks,
-                                                                        stream);
-    return;
-  }
-  ddd::launch::integrate_runtime(kRows, kWR, f64, hoist, m->dp, a, blocks, stream);
-}
-
-// The persistent launch of fixed-stencil models and one-layer nets (rhs_lean.h): one
-// instantiation per (taps, derivatives, stencil-column pairs).
-template <int kK, int kD>
-void launch_lean_kd(int pairs, const ddd::DevParams& dp, const ddd::IntegrateArgs& a, int blocks,
-                    hipStream_t stream) {
-  if (pairs == 3)
-    hipLaunchKernelGGL((ddd::lean::integrate_kernel<kK, kD, 3>), dim3(blocks), dim3(64), 0, stream, dp, a);
-  else
-    hipLaunchKernelGGL((ddd::lean::integrate_kernel<kK, kD, 4>), dim3(blocks), dim3(64), 0, stream, dp, a);
-}
-bool launch_lean(const ddd_model* m, const ddd::IntegrateArgs& a, hipStream_t stream) {
-  const ddd::DevParams& dp = m->dp;
-  if (!ddd::lean::supports(dp)) return false;
-  const int taps = dp.fixed ? 0 : dp.linear_taps, pairs = ddd::lean::column_pairs(dp.G);
-  const int blocks = (a.batch + 64 / dp.N - 1) / (64 / dp.N);
-  const int derivs = dp.D;
-#define DDD_LEAN_CASE(TAPS, DERIVS) \
-  if (taps == TAPS && derivs == DERIVS) {                                 \
-    launch_lean_kd<TAPS, DERIVS>(pairs, dp, a, blocks, stream);           \
-    return true;                                                          \
-  }
-  DDD_LEAN_CASE(0, 1) DDD_LEAN_CASE(0, 2) DDD_LEAN_CASE(0, 3) DDD_LEAN_CASE(0, 4)
-  DDD_LEAN_CASE(3, 1) DDD_LEAN_CASE(3, 2) DDD_LEAN_CASE(3, 3)
-  DDD_LEAN_CASE(5, 1) DDD_LEAN_CASE(5, 2) DDD_LEAN_CASE(5, 3)
-  DDD_LEAN_CASE(7, 1) DDD_LEAN_CASE(7, 2)
-#undef DDD_LEAN_CASE
-  return false;   // (other tap counts: the MFMA-path kernels with the tower skipped)
+Plan plan_substep(const ddd_model* m, const ddd::SubstepArgs& a) {
+  return plan_launch(m, Op::substep, substep_facts(a));
 }
 
 template <typename ST>
-int launch_integrate(ddd_model* m, ddd::IntegrateArgs a, hipStream_t stream) {
+int launch_integrate(ddd_model* m, const Plan& p, ddd::IntegrateArgs a, hipStream_t stream) {
   if (a.batch == 0 || a.n_steps == 0) return DDD_OK;
-  m->last_batch = a.batch;
-  m->last_launch_streamed = false; m->last_launch_lean = false;
+  m->last_plan = p;
 #ifdef DDD_PROBES   // profiling knobs (ddd_debug_set_option; profiles/r1_ablation.txt)
   a.prio_split = g_debug.prio_split;
   a.stagger = g_debug.stagger;
   a.trace = reinterpret_cast<unsigned long long*>(g_debug.trace_ptr);
   a.ablate = g_debug.ablate;
 #endif
-  m->last_launch_split = false;
-  m->last_launch_quad = false; m->last_launch_half = false;
-  if (m->kernel == DDD_KERNEL_MFMA && std::is_same<ST, float>::value && !m->explicit_kernel &&
-      !g_debug.no_lean && launch_lean(m, a, stream)) {
-    // fixed stencils / one-layer nets, float32 state, whole samples per wavefront: the
-    // lane == grid point kernel (no matrix work to schedule around)
-    m->last_launch_lean = true;
-    DDD_HIP(hipGetLastError());
-    return DDD_OK;
-  }
-  if (m->kernel == DDD_KERNEL_MFMA) {
-    MfmaGeometry geo = mfma_geometry(m, a.batch);
-    if (geo.rows == 64 && geo.wave_rows == 64 && std::is_same<ST, float>::value &&
-        m->split_auto && !m->explicit_kernel && m->dp.w_final4_split != nullptr &&
-        spec_equation(m, 64) >= 0) {
-      // small ensembles: two 32-row wavefronts per sample (rhs_mfma.h kSplit)
-      // measured (profiles/r4_ablation.txt, N = 64): B = 256: 1.63 x the one-wavefront kernel (twice
-      // the SIMDs busy), B = 512: 0.97 x, B = 1024: 0.89 x (two coupled wavefronts per SIMD lose to one
-      // free-running one) -- so only below three eighths of a wavefront per SIMD
-      const int spg = 64 / m->dp.N;
-      const int groups = (a.batch + spg - 1) / spg;
-      if (8 * groups <= 3 * device_simds()) geo = {64, 32};
-      // ... and FOUR 16-row wavefronts per group (kQuad: every layer on 16x16x4 MFMAs, one
-      // group on the four SIMDs of a CU) while that leaves at most two wavefronts per SIMD
-      // (measured, profiles/r6_ablation.txt)
-      if (m->dp.w_quad != nullptr && 2 * groups <= device_simds()) geo = {64, 16};
+  constexpr bool f64 = std::is_same<ST, double>::value;
+  if (p.route == Route::lean) {
+    // one instantiation per (taps, derivatives, stencil-column pairs)
+    const int blocks = group_count(m, {64, 64}, a.batch);
+    with_lean_kernel(m->dp, [&](auto k, auto d) {
+      constexpr int K = decltype(k)::value, D = decltype(d)::value;
+      if (ddd::lean::column_pairs(m->dp.G) == 3)
+        hipLaunchKernelGGL((ddd::lean::integrate_kernel<K, D, 3>), dim3(blocks), dim3(64), 0, stream, m->dp, a);
+      else
+        hipLaunchKernelGGL((ddd::lean::integrate_kernel<K, D, 4>), dim3(blocks), dim3(64), 0, stream, m->dp, a);
+    });
+  } else if (p.route == Route::mfma) {
+    const ddd::DevParams dp = launch_params(m, p);
+    const int blocks = group_count(m, p.geo, a.batch);
+    const bool hoist = !m->dp.fixed && m->dp.L == 3;
+    if (p.eq >= 0) {
+      with_equation(p.eq, [&](auto eq) {
+        constexpr int EQ = decltype(eq)::value;
+        switch (p.tile) {
+          case Tile::half:
+            if (f64) ddd::launch::integrate_half_f64_spec<EQ>(dp, a, blocks, stream);
+            else ddd::launch::integrate_half_spec<EQ>(dp, a, blocks, stream);
+            break;
+          case Tile::quad: ddd::launch::integrate_quad_spec<EQ>(dp, a, blocks, stream); break;
+          case Tile::split: ddd::launch::integrate_split_spec<EQ>(dp, a, blocks, stream); break;
+          default: ddd::launch::integrate_spec<EQ>(p.geo.rows, f64, p.traced, dp, a, blocks, stream);
+        }
+      });
+    } else if (m->big()) {
+      with_big_tower(m, p.geo.rows, [&](auto k, auto cb, auto rows) {
+        ddd::launch::integrate_big_unit<decltype(k)::value, decltype(cb)::value,
+                                        decltype(rows)::value, f64>(dp, a, blocks, stream);
+      });
+    } else if (m->wide) {
+      with_rows(p.geo.rows, [&](auto rows) {
+        ddd::launch::integrate_wide_unit<decltype(rows)::value, f64 ? 1 : 0>(hoist, dp, a, blocks,
+                                                                            stream);
+      });
+    } else {
+      ddd::launch::integrate_runtime(p.geo.rows, p.geo.wave_rows, f64, hoist, dp, a, blocks, stream);
     }
-    // an explicit DDD_KERNEL_MFMA_ROWS64_W16 / _W32 where the model has no such kernel (float64
-    // state, no per-equation specialisation): the one-wavefront geometry
-    if (geo.rows == 64 && geo.wave_rows == 16 &&
-        !(std::is_same<ST, float>::value && m->dp.w_quad != nullptr && spec_equation(m, 64) >= 0))
-      geo = {64, 64};
-    m->last_launch_split = geo.rows == 64 && geo.wave_rows == 32;
-    m->last_launch_quad = geo.rows == 64 && geo.wave_rows == 16;
-    if (geo.rows == 64 && geo.wave_rows == 64) launch_mfma_integrate<64, 64, ST>(m, a, stream);
-    else if (geo.rows == 64 && geo.wave_rows == 16) launch_mfma_integrate<64, 16, ST>(m, a, stream);
-    else if (geo.rows == 64) launch_mfma_integrate<64, 32, ST>(m, a, stream);
-    else launch_mfma_integrate<256, 64, ST>(m, a, stream);
-  } else if (use_weno_kernel(m)) {
-    ddd::launch::weno_integrate(std::is_same<ST, double>::value, m->dp, a, stream);
+  } else if (p.route == Route::weno) {
+    ddd::launch::weno_integrate(f64, m->dp, a, stream);
   } else {
     int rc = check_generic_lds(m, (int)sizeof(ST));
     if (rc) return rc;
@@ -1369,14 +1481,13 @@ SlabPlan plan_slabs(const ddd_model* m, int batch) {
   SlabPlan plan;
   plan.half_batch[0] = batch;
   if (m->kernel != DDD_KERNEL_MFMA || m->explicit_kernel || g_debug.no_spec) return plan;
-  const MfmaGeometry geo = mfma_geometry(m, batch);
-  const int spg = geo.rows / m->dp.N;
-  const int groups = (batch + spg - 1) / spg;
-  const int capacity = geo.rows == 64 ? 2 * device_simds() : device_simds() / 2;
-  if (geo.wave_rows != 64 || spec_equation(m, geo.rows) < 0 || groups < 2 * capacity) return plan;
+  const MfmaGeometry geo = mfma_geometry(m);
+  const int groups = group_count(m, geo, batch);
+  if (geo.wave_rows != 64 || spec_equation(m, geo.rows) < 0 || groups < 2 * resident_groups(geo))
+    return plan;
   plan.halves = 2;
   if (g_debug.substep_parts > 0) plan.halves = std::min(g_debug.substep_parts, kMaxParts);
-  const int per = ((groups + plan.halves - 1) / plan.halves) * spg;   // whole workgroups
+  const int per = ((groups + plan.halves - 1) / plan.halves) * (geo.rows / m->dp.N);   // whole workgroups
   int first = 0;
   for (int i = 0; i < plan.halves; ++i) {
     plan.slab_first[i] = first;
@@ -1429,18 +1540,6 @@ int chain_close(ddd_model* m) {
   m->chain.open = false;
   m->chain.forked = false;
   return rc;
-}
-
-// The region can run on the command ring: a per-equation kernel on one-wave groups (N | 64),
-// the whole ensemble from sample 0, no derivative / coefficient views.
-bool ring_eligible(const ddd_model* m, const ddd::SubstepArgs& a) {
-  if (m->region_mode != DDD_REGION_RING) return false;   // (opt-in: measured equal to the launches)
-  if (m->kernel != DDD_KERNEL_MFMA || m->explicit_kernel || g_debug.no_spec) return false;
-  if (a.batch <= 0 || a.derivs_out != nullptr || a.coeffs_out != nullptr) return false;
-  if (use_stream_kernel(m, a)) return false;
-  MfmaGeometry geo = mfma_geometry(m, a.batch);
-  if (geo.wave_rows == 16) geo = {64, 64};
-  return geo.rows == 64 && geo.wave_rows == 64 && spec_equation(m, 64) >= 0;
 }
 
 int ring_create(ddd_model* m) {
@@ -1497,8 +1596,9 @@ void ring_destroy(ddd_model* m) {
   m->ring = nullptr;
 }
 
-// One command = one ddd_rk_substep call.  Starts the persistent kernel when none is waiting.
-int ring_post(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream) {
+// One command = one ddd_rk_substep call (p: a plan of Op::ring).  Starts the persistent
+// kernel when none is waiting.
+int ring_post(ddd_model* m, const Plan& p, const ddd::SubstepArgs& a, hipStream_t stream) {
   if (m->ring == nullptr) { int rc = ring_create(m); if (rc) return rc; }
   Ring* rg = m->ring;
   std::unique_lock<std::mutex> lk(rg->mu);
@@ -1509,27 +1609,15 @@ int ring_post(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream) {
   }
   if (rg->running && rg->stream != stream) (void)ring_stop_locked(rg);
   if (!rg->running) {
-    m->dp.dpp_rol = dpp_wave_rol_ok();
-    const int spg = 64 / m->dp.N;
-    const int groups = (a.batch + spg - 1) / spg;
-    rg->grid = std::min(groups, 2 * device_simds());
+    const ddd::DevParams dp = launch_params(m, p);
+    rg->grid = std::min(group_count(m, p.geo, a.batch), resident_groups(p.geo));
     ddd::RingArgs r{};
     r.slots = rg->slots; r.dev_slots = rg->d_slots; r.count = rg->d_count; r.done = rg->done; r.status = rg->status;
     r.first_index = (unsigned)rg->next_index;
     r.watchdog_ticks = rg->watchdog_ms * 100000u;   // 100 MHz
-    const int eq = spec_equation(m, 64);
-#define DDD_RING_CASE(EQ) \
-    case EQ: ddd::launch::substep_ring_spec<EQ>(m->dp, r, rg->grid, stream); break;
-    switch (eq) {
-      DDD_RING_CASE(ddd::EQ_BURGERS)
-      DDD_RING_CASE(ddd::EQ_BURGERS_CONS)
-      DDD_RING_CASE(ddd::EQ_KDV)
-      DDD_RING_CASE(ddd::EQ_KDV_CONS)
-      DDD_RING_CASE(ddd::EQ_KS)
-      DDD_RING_CASE(ddd::EQ_KS_CONS)
-      default: return fail(DDD_ERR_UNSUPPORTED, "command ring: no per-equation kernel");
-    }
-#undef DDD_RING_CASE
+    with_equation(p.eq, [&](auto eq) {
+      ddd::launch::substep_ring_spec<decltype(eq)::value>(dp, r, rg->grid, stream);
+    });
     DDD_HIP(hipGetLastError());
     rg->running = true;
     rg->stream = stream;
@@ -1561,9 +1649,7 @@ int ring_post(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream) {
   ++rg->next_index;
   ++rg->commands;
   rg->last_post = std::chrono::steady_clock::now();
-  m->last_batch = a.batch;
-  m->last_launch_streamed = false; m->last_launch_lean = false;
-  m->last_launch_split = false; m->last_launch_quad = false; m->last_launch_half = false;
+  m->last_plan = p;
   return DDD_OK;
 }
 
@@ -1574,14 +1660,15 @@ int ring_post(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream) {
 int substep_entry(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream) {
   ddd_model::Chain& ch = m->chain;
   if (!ch.open || stream != ch.stream || a.derivs_out != nullptr || a.coeffs_out != nullptr)
-    return launch_substep(m, a, stream);
-  if (ring_eligible(m, a)) {
+    return launch_substep(m, plan_substep(m, a), a, stream);
+  const Plan p = plan_launch(m, Op::ring, substep_facts(a));
+  if (p.op == Op::ring) {
     if (ch.forked && ch.halves > 1) {   // (a region that started on the two chains)
       int rc = join_lanes(m, stream, ch.halves);
       ch.forked = false;
       if (rc) return rc;
     }
-    return ring_post(m, a, stream);
+    return ring_post(m, p, a, stream);
   }
   if (m->ring != nullptr) {   // this call takes launches: behind every command posted so far
     std::lock_guard<std::mutex> lk(m->ring->mu);
@@ -1605,7 +1692,7 @@ int substep_entry(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream) {
       if (rc) { ch.forked = false; return rc; }
     }
   }
-  if (ch.halves <= 1) return launch_substep(m, a, stream);
+  if (ch.halves <= 1) return launch_substep(m, p, a, stream);
   int rc = DDD_OK;
   for (int hf = 0; hf < ch.halves && rc == DDD_OK; ++hf) {
     if (ch.half_batch[hf] == 0) continue;
@@ -1617,9 +1704,8 @@ int substep_entry(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream) {
     if (a.y_out != nullptr) h.y_out = a.y_out + off;
     if (a.acc_in != nullptr) h.acc_in = a.acc_in + off;
     if (a.acc_out != nullptr) h.acc_out = a.acc_out + off;
-    rc = launch_substep(m, h, m->aux_stream[hf], ch.slab_first[hf], ch.halves);
+    rc = launch_substep(m, plan_substep(m, h), h, m->aux_stream[hf], ch.slab_first[hf], ch.halves);
   }
-  m->last_batch = a.batch;
   if (rc) {   // do not leave the internal streams running ahead of a failed call
     (void)join_lanes(m, stream, ch.halves);
     ch.forked = false;
@@ -2065,7 +2151,6 @@ int launch_spectral(ddd_model* m, const ddd::spectral::SubstepArgs64& a, hipStre
   hipLaunchKernelGGL(ddd::spectral::substep_kernel, dim3(a.batch),
                      dim3(ddd::spectral::kThreads), lds, stream, m->sp, a);
   DDD_HIP(hipGetLastError());
-  m->last_batch = a.batch;
   return DDD_OK;
 }
 }  // namespace
@@ -2307,7 +2392,7 @@ int ddd_space_derivatives(ddd_model* m, const float* y, float* out, int batch,
     return fail(DDD_ERR_UNSUPPORTED, "model_target has no spatial derivatives");
   ddd::SubstepArgs a{};
   a.y_in = y; a.derivs_out = out; a.batch = batch;
-  return launch_substep(m, a, static_cast<hipStream_t>(stream));
+  return launch_substep(m, plan_substep(m, a), a, static_cast<hipStream_t>(stream));
 }
 
 int ddd_coefficients(ddd_model* m, const float* y, float* out, int batch, void* stream) {
@@ -2319,7 +2404,7 @@ int ddd_coefficients(ddd_model* m, const float* y, float* out, int batch, void* 
     return fail(DDD_ERR_UNSUPPORTED, "model_target does not produce coefficients");
   ddd::SubstepArgs a{};
   a.y_in = y; a.coeffs_out = out; a.batch = batch;
-  return launch_substep(m, a, static_cast<hipStream_t>(stream));
+  return launch_substep(m, plan_substep(m, a), a, static_cast<hipStream_t>(stream));
 }
 
 int ddd_integrate_fixed(ddd_model* m, int scheme, int launch_mode, double t0, double dt,
@@ -2337,7 +2422,7 @@ int ddd_integrate_fixed(ddd_model* m, int scheme, int launch_mode, double t0, do
     a.t0 = t0; a.dt = dt; a.n_steps = n_steps; a.save_every = save_every; a.tab = tab;
     a.sc = make_stage_consts(tab, dt);
     a.y0 = y0; a.y_out = y_out; a.batch = batch;
-    return launch_integrate<float>(m, a, stream);
+    return launch_integrate<float>(m, plan_launch(m, Op::persistent, {batch}), a, stream);
   }
   if (launch_mode != DDD_LAUNCH_PER_SUBSTEP && launch_mode != DDD_LAUNCH_PER_STEP)
     return fail(DDD_ERR_INVALID_ARGUMENT, "unknown launch_mode %d", launch_mode);
@@ -2353,21 +2438,18 @@ int ddd_integrate_fixed(ddd_model* m, int scheme, int launch_mode, double t0, do
   const float h = (float)dt;
   const ddd::StageConsts stage_consts = make_stage_consts(tab, dt);
 
-  m->last_launch_half = false; m->last_launch_quad = false; m->last_launch_split = false;
   // large ensembles: two half-ensembles side by side (plan_slabs)
   const SlabPlan plan = plan_slabs(m, batch);
   const int halves = plan.halves;
   const int* half_batch = plan.half_batch;
   const int* slab_first = plan.slab_first;
-  int step_eq = -1;   // per-equation kernel for DDD_LAUNCH_PER_STEP
-  if (m->kernel == DDD_KERNEL_MFMA && !m->explicit_kernel && !g_debug.no_spec) {
-    const MfmaGeometry geo = mfma_geometry(m, batch);
-    if (geo.wave_rows == 64 && launch_mode == DDD_LAUNCH_PER_STEP)
-      step_eq = spec_equation(m, geo.rows);
-  }
-  if (launch_mode == DDD_LAUNCH_PER_STEP && ddd::stream::step_supports(m->dp) &&
-      !m->explicit_kernel && !g_debug.no_stream && aligned16(y0) && aligned16(y_out) &&
-      (elems % 4) == 0) {
+  // DDD_LAUNCH_PER_STEP: a kernel that takes all stages of a step, if there is one
+  Plan step_plan;
+  if (launch_mode == DDD_LAUNCH_PER_STEP)
+    step_plan = plan_launch(m, Op::step, {batch, false, false, false,
+                                          aligned16(y0) && aligned16(y_out) && (elems % 4) == 0});
+  if (step_plan.op == Op::step) m->last_plan = step_plan;
+  if (step_plan.route == Route::stream_fixed) {
     // fixed stencils, all stages of a step in one launch of the streaming kernel: the
     // stage inputs stay in the block's LDS tile, 8 B per grid point and step;
     // persistent blocks (eight per CU) walk over the tiles
@@ -2387,8 +2469,6 @@ int ddd_integrate_fixed(ddd_model* m, int scheme, int launch_mode, double t0, do
       if (saving) ++snap;
     }
     DDD_HIP(hipGetLastError());
-    m->last_batch = batch;
-    m->last_launch_streamed = true; m->last_launch_lean = false;
     return DDD_OK;
   }
   hipStream_t lanes[kMaxParts] = {stream, stream, stream, stream};
@@ -2408,46 +2488,28 @@ int ddd_integrate_fixed(ddd_model* m, int scheme, int launch_mode, double t0, do
     const double t = t0 + (double)step * dt;
     const bool saving = (step + 1) % save_every == 0;
     float* ynew = saving ? y_out + snap * elems : (y == ping ? pong : ping);
-    if (step_eq >= 0) {
+    if (step_plan.op == Op::step) {
       // all stages in one launch per half-ensemble (step_multi_kernel)
-      m->dp.dpp_rol = dpp_wave_rol_ok();
-      const MfmaGeometry geo = mfma_geometry(m, batch);
-      const int spg = geo.rows / m->dp.N;
-      const int capacity = (geo.rows == 64 ? 2 * device_simds() : device_simds() / 2) / halves;
       for (int hf = 0; hf < halves; ++hf) {
         if (half_batch[hf] == 0) continue;
-        ddd::DevParams dp = m->dp;
-        if (slab_first[hf] != 0 && dp.forced) {
-          dp.frc += (size_t)slab_first[hf] * dp.P;
-          dp.runs += (size_t)slab_first[hf] * 8;
-        }
+        const ddd::DevParams dp = launch_params(m, step_plan, slab_first[hf]);
         ddd::StepArgs sa{};
         sa.t = t; sa.dt = dt; sa.tab = tab; sa.sc = stage_consts;
         sa.y_in = y + half_off[hf]; sa.y_out = ynew + half_off[hf]; sa.batch = half_batch[hf];
-        const int groups = (half_batch[hf] + spg - 1) / spg;
-        const int grid = std::min(groups, capacity);
-        const bool half = step_eq >= 0 && geo.rows == 64 && m->d_w_hidden_half != nullptr &&
-                          m->d_w_final4_half != nullptr && m->d_w_t16 != nullptr && !g_debug.no_half;
-        m->last_launch_half = half;
-        if (half) { dp.w_hidden = m->d_w_hidden_half; dp.w_final4 = m->d_w_final4_half; dp.w_quad = m->d_w_t16; }
-        switch (step_eq) {
-#define DDD_STEP_CASE(EQ) \
-          case EQ:                                                                              \
-            if (half) ddd::launch::step_half_spec<EQ>(dp, sa, groups, grid, lanes[hf]);         \
-            else ddd::launch::step_spec<EQ>(geo.rows, dp, sa, groups, grid, lanes[hf]);         \
-            break;
-          DDD_STEP_CASE(ddd::EQ_BURGERS) DDD_STEP_CASE(ddd::EQ_BURGERS_CONS)
-          DDD_STEP_CASE(ddd::EQ_KDV) DDD_STEP_CASE(ddd::EQ_KDV_CONS)
-          DDD_STEP_CASE(ddd::EQ_KS) DDD_STEP_CASE(ddd::EQ_KS_CONS)
-#undef DDD_STEP_CASE
-          default: break;
-        }
+        const int groups = group_count(m, step_plan.geo, half_batch[hf]);
+        const int grid = std::min(groups, resident_groups(step_plan.geo) / halves);
+        with_equation(step_plan.eq, [&](auto eq) {
+          constexpr int EQ = decltype(eq)::value;
+          if (step_plan.tile == Tile::half)
+            ddd::launch::step_half_spec<EQ>(dp, sa, groups, grid, lanes[hf]);
+          else
+            ddd::launch::step_spec<EQ>(step_plan.geo.rows, dp, sa, groups, grid, lanes[hf]);
+        });
       }
       if (hipGetLastError() != hipSuccess) {
         rc = fail(DDD_ERR_HIP, "step launch failed");
         break;
       }
-      m->last_launch_streamed = false; m->last_launch_lean = false;
       y = ynew;
       if (saving) ++snap;
       continue;
@@ -2474,7 +2536,7 @@ int ddd_integrate_fixed(ddd_model* m, int scheme, int launch_mode, double t0, do
         a.trace = reinterpret_cast<unsigned long long*>(g_debug.walk_trace_ptr);
         a.trace_row0 = walk_launch++ * ddd::kWalkTraceRows;
 #endif
-        rc = launch_substep(m, a, lanes[hf], slab_first[hf], halves);
+        rc = launch_substep(m, plan_substep(m, a), a, lanes[hf], slab_first[hf], halves);
         if (rc) break;
       }
       if (rc) break;
@@ -2487,7 +2549,6 @@ int ddd_integrate_fixed(ddd_model* m, int scheme, int launch_mode, double t0, do
   if (halves > 1) {
     const int rc_join = join_lanes(m, stream, halves);
     if (rc == DDD_OK) rc = rc_join;
-    m->last_batch = batch;
   }
   return rc;
 }
@@ -2551,7 +2612,8 @@ int ddd_integrate_fixed_f64(ddd_model* m, int scheme, double t0, double dt, int 
   a.t0 = t0; a.dt = dt; a.n_steps = n_steps; a.save_every = save_every;
   a.sc = make_stage_consts(a.tab, dt);
   a.y0 = y0; a.y_out = y_out; a.batch = batch;
-  return launch_integrate<double>(m, a, static_cast<hipStream_t>(stream));
+  return launch_integrate<double>(m, plan_launch(m, Op::persistent, {batch, true}), a,
+                                  static_cast<hipStream_t>(stream));
 }
 
 int ddd_integrate_adaptive_f64(ddd_model* m, const double* times, int n_times, double rtol,
@@ -2625,10 +2687,9 @@ int ddd_integrate_adaptive_f64(ddd_model* m, const double* times, int n_times, d
     max_attempts = (long long)std::min(1e15, std::ceil(span / max_step) * 1000.0 + 100000.0);
   }
   a.max_attempts = max_attempts;
-  m->last_batch = batch;
-  m->last_launch_streamed = false; m->last_launch_lean = false;
-  m->last_launch_split = false; m->last_launch_quad = false; m->last_launch_half = false;
-  if (m->spectral) {
+  const Plan p = plan_launch(m, Op::adaptive, {batch, true});
+  m->last_plan = p;
+  if (p.route == Route::spectral) {
     // float64 right-hand side (SpectralDifferentiator), one workgroup per sample
     const size_t lds = ddd::spectral::lds_bytes(m->sp);
     const int pts = (m->sp.N + ddd::spectral::kThreads - 1) / ddd::spectral::kThreads;
@@ -2647,12 +2708,12 @@ int ddd_integrate_adaptive_f64(ddd_model* m, const double* times, int n_times, d
 #undef DDD_SPECTRAL_ADAPTIVE
     return enqueued();
   }
-  if (use_weno_kernel(m)) {
+  if (p.route == Route::weno) {
     // the WENO5 + Godunov-flux exact solver: one wavefront and one controller per sample
     ddd::launch::weno_adaptive(m->dp, a, stream);
     return enqueued();
   }
-  if (m->kernel != DDD_KERNEL_MFMA) {
+  if (p.route == Route::generic) {
     // generic right-hand side (nets the MFMA path does not carry, WENO on grids that are
     // not 64 x {1, 2, 4, 8} points): one workgroup and one controller per sample
     const size_t lds = ddd::generic::adaptive_lds_bytes(m->dp);
@@ -2665,69 +2726,25 @@ int ddd_integrate_adaptive_f64(ddd_model* m, const double* times, int n_times, d
                        lds, stream, m->dp, a);
     return enqueued();
   }
-  m->dp.dpp_rol = dpp_wave_rol_ok();
-  MfmaGeometry geo = mfma_geometry(m, batch);
-  const bool want_quad = geo.rows == 64 && (geo.wave_rows == 16 || (geo.wave_rows == 64 && m->force_rows == 0));
-  if (geo.wave_rows != 64) geo = {64, 64};   // the two-wave split has no adaptive instantiation
-  const int spg = geo.rows / m->dp.N;
-  const int blocks = (batch + spg - 1) / spg;
-  // small ensembles: every 64-row group on four 16-row wavefronts (rhs_mfma.h kQuad), as
-  // launch_integrate chooses it for the fixed-step integrators -- the reference's callers
-  // integrate tens to hundreds of samples (scripts/run_evaluation.py:212-221)
-  m->last_launch_quad = false; m->last_launch_half = false;
-  if (want_quad && m->dp.w_quad != nullptr && spec_equation(m, 64) >= 0 &&
-      (m->force_rows == 16 || (m->split_auto && !m->explicit_kernel && 2 * blocks <= device_simds()))) {
-    m->last_launch_quad = true;
-    switch (spec_equation(m, 64)) {
-#define DDD_ADAPTIVE_QUAD(EQ) \
-      case EQ: ddd::launch::adaptive_quad_spec<EQ>(m->dp, a, blocks, stream); break;
-      DDD_ADAPTIVE_QUAD(ddd::EQ_BURGERS)
-      DDD_ADAPTIVE_QUAD(ddd::EQ_BURGERS_CONS)
-      DDD_ADAPTIVE_QUAD(ddd::EQ_KDV)
-      DDD_ADAPTIVE_QUAD(ddd::EQ_KDV_CONS)
-      DDD_ADAPTIVE_QUAD(ddd::EQ_KS)
-      DDD_ADAPTIVE_QUAD(ddd::EQ_KS_CONS)
-#undef DDD_ADAPTIVE_QUAD
-      default: break;
-    }
-    return enqueued();
-  }
-  // nets of up to 16 filters: the block-diagonal tower (one-wave groups)
-  const bool half = geo.rows == 64 && m->d_w_hidden_half != nullptr && m->d_w_final4_half != nullptr &&
-                    spec_equation(m, 64) >= 0 && !g_debug.no_half;
-  m->last_launch_half = half;
-  ddd::DevParams dp_half = m->dp;
-  if (half) { dp_half.w_hidden = m->d_w_hidden_half; dp_half.w_final4 = m->d_w_final4_half; dp_half.w_quad = m->d_w_t16; }
-  switch (spec_equation(m, geo.rows)) {
-#define DDD_ADAPTIVE_CASE(EQ) \
-    case EQ:                                                                        \
-      if (half) ddd::launch::adaptive_half_spec<EQ>(dp_half, a, blocks, stream);    \
-      else ddd::launch::adaptive_spec<EQ>(geo.rows, m->dp, a, blocks, stream);      \
-      break;
-    DDD_ADAPTIVE_CASE(ddd::EQ_BURGERS)
-    DDD_ADAPTIVE_CASE(ddd::EQ_BURGERS_CONS)
-    DDD_ADAPTIVE_CASE(ddd::EQ_KDV)
-    DDD_ADAPTIVE_CASE(ddd::EQ_KDV_CONS)
-    DDD_ADAPTIVE_CASE(ddd::EQ_KS)
-    DDD_ADAPTIVE_CASE(ddd::EQ_KS_CONS)
-#undef DDD_ADAPTIVE_CASE
-    default:
-      if (m->big()) {
-#define DDD_BIG_ADAPTIVE(K, CB)                                                           \
-        if (m->tower_k == K && m->tower_cb == CB) {                                       \
-          if (geo.rows == 64) ddd::launch::adaptive_big_unit<K, CB, 64>(m->dp, a, blocks, stream); \
-          else ddd::launch::adaptive_big_unit<K, CB, 256>(m->dp, a, blocks, stream);      \
-        }
-        DDD_FOR_EACH_BIG_TOWER(DDD_BIG_ADAPTIVE)
-#undef DDD_BIG_ADAPTIVE
-      } else if (m->wide) {
-        if (geo.rows == 64) ddd::launch::adaptive_wide_unit<64>(m->dp, a, blocks, stream);
-        else ddd::launch::adaptive_wide_unit<256>(m->dp, a, blocks, stream);
-      } else if (geo.rows == 64) {
-        ddd::launch::adaptive_runtime_unit<64>(m->dp, a, blocks, stream);
-      } else {
-        ddd::launch::adaptive_runtime_unit<256>(m->dp, a, blocks, stream);
-      }
+  const ddd::DevParams dp = launch_params(m, p);
+  const int blocks = group_count(m, p.geo, batch);
+  if (p.eq >= 0) {
+    with_equation(p.eq, [&](auto eq) {
+      constexpr int EQ = decltype(eq)::value;
+      if (p.tile == Tile::quad) ddd::launch::adaptive_quad_spec<EQ>(dp, a, blocks, stream);
+      else if (p.tile == Tile::half) ddd::launch::adaptive_half_spec<EQ>(dp, a, blocks, stream);
+      else ddd::launch::adaptive_spec<EQ>(p.geo.rows, dp, a, blocks, stream);
+    });
+  } else if (m->big()) {
+    with_big_tower(m, p.geo.rows, [&](auto k, auto cb, auto rows) {
+      ddd::launch::adaptive_big_unit<decltype(k)::value, decltype(cb)::value, decltype(rows)::value>(
+          dp, a, blocks, stream);
+    });
+  } else {
+    with_rows(p.geo.rows, [&](auto rows) {
+      if (m->wide) ddd::launch::adaptive_wide_unit<decltype(rows)::value>(dp, a, blocks, stream);
+      else ddd::launch::adaptive_runtime_unit<decltype(rows)::value>(dp, a, blocks, stream);
+    });
   }
   return enqueued();
 }
@@ -2913,10 +2930,12 @@ int ddd_set_kernel(ddd_model* m, int kind) {
       m->kernel = m->mfma_ok ? DDD_KERNEL_MFMA : DDD_KERNEL_GENERIC;
       m->force_rows = 0;
       m->explicit_kernel = false;
+      m->last_plan = Plan{};
       return DDD_OK;
     case DDD_KERNEL_GENERIC:
       m->kernel = DDD_KERNEL_GENERIC;
       m->explicit_kernel = true;
+      m->last_plan = Plan{};
       return DDD_OK;
     case DDD_KERNEL_MFMA:
     case DDD_KERNEL_MFMA_ROWS64:
@@ -2945,24 +2964,28 @@ int ddd_set_kernel(ddd_model* m, int kind) {
                       : kind == DDD_KERNEL_MFMA_ROWS64_W32 ? 32
                       : kind == DDD_KERNEL_MFMA_ROWS64_W16 ? 16
                       : kind == DDD_KERNEL_MFMA_ROWS256 ? 256 : 0;
+      m->last_plan = Plan{};
       return DDD_OK;
     default:
       return fail(DDD_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", kind);
   }
 }
 
+// The name of the plan the most recent launch ran.  With no launch recorded (a fresh
+// handle, or ddd_set_kernel since the last launch): spectral, then WENO, then generic, then
+// the MFMA name of the geometry alone (mfma_geometry: r256, r64w32 or r64).
 const char* ddd_kernel_name(const ddd_model* m) {
   if (m == nullptr) return "";
-  if (m->spectral) return "spectral_f64";
-  if (m->last_launch_streamed) return "stream_fixed";
-  if (m->last_launch_lean) return "valu_f32_lean";
-  if (use_weno_kernel(m)) return "valu_f32_weno";
-  if (m->kernel != DDD_KERNEL_MFMA) return "generic";
-  const MfmaGeometry geo = mfma_geometry(m, m->last_batch > 0 ? m->last_batch : 1 << 30);
-  if (geo.rows == 256) return "mfma_f32_r256";
-  if (m->last_launch_quad) return "mfma_f32_r64w16";
-  if (m->last_launch_half) return "mfma_f32_r64h16";
-  return (geo.wave_rows == 32 || m->last_launch_split) ? "mfma_f32_r64w32" : "mfma_f32_r64";
+  if (m->last_plan.name != nullptr) return m->last_plan.name;
+  Plan p;
+  p.route = m->spectral ? Route::spectral
+            : use_weno_kernel(m) ? Route::weno
+            : m->kernel != DDD_KERNEL_MFMA ? Route::generic : Route::mfma;
+  if (p.route == Route::mfma) {
+    p.geo = mfma_geometry(m);
+    if (p.geo.wave_rows == 32) p.tile = Tile::split;
+  }
+  return plan_name(p);
 }
 
 int64_t ddd_fma_per_point(const ddd_model* m) { return m ? m->fma_per_point : 0; }
