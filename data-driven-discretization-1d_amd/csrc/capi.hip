@@ -54,7 +54,7 @@ struct DebugOptions {
   int no_lean = 0;       // the MFMA-path kernels (tower skipped) instead of rhs_lean.h
   int no_weno = 0;       // the generic kernel instead of rhs_weno.h
   int no_fft = 0;        // spectral models: the O(N^2) circulant form at every N
-  int no_half = 0;       // nets of <= 16 filters: embedded in 32 instead of the block-diagonal tower
+  int no_half = 0;       // nets of <= 16 filters: embedded in 32 instead of the 16-channel tiles
   int prio_split = 0;    // A/B: static wave priorities
   int stagger = 0;       // A/B: initial s_sleep of odd wave slots
   int substep_parts = 0; // A/B: sample slabs advanced side by side in the per-substep modes (0: auto)
@@ -281,7 +281,7 @@ struct MfmaGeometry { int rows, wave_rows; };
 enum class Op { substep, step, persistent, adaptive, ring };
 enum class Route { spectral, stream_fixed, lean, weno, generic, mfma };
 // 64-row MFMA groups on one, two (kSplit) or four (kQuad) wavefronts, or one wavefront on the
-// 16-channel tiles of nets of up to 16 filters (HalfTower / Tile16Tower)
+// 16-channel tiles of nets of up to 16 filters (Tile16Tower)
 enum class Tile { one_wave, split, quad, half };
 
 struct Plan {
@@ -318,9 +318,8 @@ struct ddd_model {
   float* d_w_final4_rt = nullptr;
   float* d_w_final4_split = nullptr;
   float* d_w_quad = nullptr;
-  float* d_w_hidden_half = nullptr;   // block-diagonal packing of a <= 16-filter net (rhs_mfma.h HalfTower)
-  float* d_w_final4_half = nullptr;
-  float* d_w_t16 = nullptr;           // the same net as 16x16x4 A operands (rhs_mfma.h Tile16Tower)
+  float* d_w_final4_half = nullptr;   // output layer of a <= 16-filter net (rhs_mfma.h Tile16Tower)
+  float* d_w_t16 = nullptr;           // its input and hidden layers as 16x16x4 A operands
   bool wide = false;                 // run-time kernels of the wide flavour (rhs_mfma.h kWide)
   int tower_k = 5, tower_cb = 1;     // conv tower the MFMA kernels carry the net in (rhs_mfma.h Tower)
   bool big() const { return tower_k != ddd::mfma::kKW || tower_cb != 1; }
@@ -496,7 +495,7 @@ int pack_mfma_weights(ddd_model* m, const NetLayout& net) {
   // relu towers run on activations scaled by 2^-kReluShift (dev_params.h: the relu is the
   // VALU's [0, 1] clamp on a packed add): the input layer's weights and every bias row of
   // the tower carry `dn`, the output layer's weights `up`.  Exact: powers of two.
-  const bool relu_clamp = dp.act == ddd::ACT_RELU && ddd::kReluShift != 0;
+  const bool relu_clamp = dp.act == ddd::ACT_RELU;
   const float dn = relu_clamp ? std::ldexp(1.0f, -ddd::kReluShift) : 1.0f;
   const float up = relu_clamp ? std::ldexp(1.0f, ddd::kReluShift) : 1.0f;
   if (m->big()) {
@@ -807,26 +806,13 @@ int pack_mfma_weights(ddd_model* m, const NetLayout& net) {
         if (rc) return rc;
         m->dp.w_quad = m->d_w_quad;
       }
-      // ... and, for nets of up to 16 filters (embedded here in 32), the BLOCK-DIAGONAL packing
-      // of rhs_mfma.h HalfTower: the hidden layer's panel with output rows 16..31 = the same 16
-      // channels fed by reduction half 1, and the output layer over 5 x 16 + 1 reduction steps.
-      // Source: the embedded net (channels >= 16 are zero there).
+      // ... and, for nets of up to 16 filters (embedded here in 32), the packing of rhs_mfma.h
+      // Tile16Tower: the output layer over 5 x 16 + 1 reduction steps, the input and hidden
+      // layers as 16x16x4 A operands.  Source: the embedded net (channels >= 16 are zero there).
       if (dp.L == 3 && dp.cout[0] <= 16 && m->dp.fin4_groups <= 4) {
         using namespace ddd::mfma;
         const float* w1 = weights + net.w_off[1];   // [5][32][32]
         const float* b1 = weights + net.b_off[1];
-        std::vector<float> hid((size_t)kHidSteps * 64, 0.0f);
-        for (int s2 = 0; s2 < 80; ++s2) {
-          const int tap = s2 / 16, jj = s2 % 16;
-          for (int lane = 0; lane < 64; ++lane) {
-            const int mrow = lane & 31, half = lane >> 5;
-            if ((mrow < 16) == (half == 0))
-              hid[(size_t)s2 * 64 + lane] = w1[(tap * 32 + jj) * 32 + (mrow & 15)];
-          }
-        }
-        for (int lane = 0; lane < 32; ++lane) hid[(size_t)80 * 64 + lane] = dn * b1[lane & 15];
-        rc = upload(quad_rows(hid.data(), kHidSteps), &m->d_w_hidden_half);
-        if (rc) return rc;
         const float* w = m->spec_folded ? wf.data() : w_nat;
         const float* b = m->spec_folded ? bf.data() : b_nat;
         const int cout_n = m->spec_folded ? fold_cols : dp.C_out;
@@ -845,7 +831,7 @@ int pack_mfma_weights(ddd_model* m, const NetLayout& net) {
           }
         rc = upload(quad_rows(fin.data(), fin4_regs(4)), &m->d_w_final4_half);
         if (rc) return rc;
-        // ... and as A operands of the 16x16x4 layers (Tile16Tower): lane l = W[out = l & 15][slot l >> 4];
+        // the 16x16x4 A operands: lane l = W[out = l & 15][slot l >> 4];
         // input layer: step 0 = taps 0..3, step 1 = tap 4, bias, 0, 0; hidden layer: step 4 tap + e,
         // slot sg -> input channel 4 e + sg; step 20: the bias in slot 0
         const float* w0 = weights + net.w_off[0];   // [5][1][32]
@@ -939,9 +925,8 @@ void decide_mfma(ddd_model* m) {
     m->tower_cb = dp.F <= 32 ? 1 : 2;
     if (m->tower_cb == 2 && m->tower_k == 3) m->tower_k = 5;   // (64-filter towers: 5 and 7 taps)
     // up to 16 filters of up to 3 taps in the architecture of the per-equation kernels: the
-    // 5 x 32 tower, whose persistent integrators carry such nets block-diagonally (rhs_mfma.h
-    // HalfTower: half the hidden-layer MFMAs of the embedding) -- ahead of the 3-tap tower,
-    // where they would occupy a quarter of every MFMA
+    // 5 x 32 tower, whose persistent integrators carry such nets on 16-channel tiles (rhs_mfma.h
+    // Tile16Tower) -- ahead of the 3-tap tower, where they would occupy a quarter of every MFMA
     if (m->tower_k == 3 && dp.F <= 16 && dp.L == 3 && dp.act == ddd::ACT_RELU && !wide &&
         dp.target == ddd::TARGET_COEFFICIENTS && dp.pao > 0 &&
         dp.equation >= ddd::EQ_BURGERS && dp.equation <= ddd::EQ_KS_CONS &&
@@ -1250,7 +1235,7 @@ void plan_mfma(const ddd_model* m, const CallFacts& f, Plan* p) {
   p->tile = geo.wave_rows == 32 ? Tile::split : geo.wave_rows == 16 ? Tile::quad : Tile::one_wave;
   // nets of up to 16 filters: the 16-channel tiles of the per-equation one-wave kernels
   if (p->tile == Tile::one_wave && geo.rows == 64 && eq >= 0 && !p->traced &&
-      m->d_w_hidden_half != nullptr && m->d_w_final4_half != nullptr && m->d_w_t16 != nullptr &&
+      m->d_w_final4_half != nullptr && m->d_w_t16 != nullptr &&
       !g_debug.no_half)
     p->tile = Tile::half;
 }
@@ -1314,7 +1299,6 @@ ddd::DevParams launch_params(ddd_model* m, const Plan& p, int sample0 = 0) {
     dp.runs += (size_t)sample0 * 8;
   }
   if (p.tile == Tile::half) {
-    dp.w_hidden = m->d_w_hidden_half;
     dp.w_final4 = m->d_w_final4_half;
     dp.w_quad = m->d_w_t16;
   }
@@ -2188,7 +2172,7 @@ int ddd_model_destroy(ddd_model* m) {
   free_dev(m->d_weights); free_dev(m->d_weights4); free_dev(m->d_nullspace); free_dev(m->d_bias);
   free_dev(m->d_w_hidden);
   free_dev(m->d_w_input);
-  free_dev(m->d_w_hidden_half); free_dev(m->d_w_final4_half); free_dev(m->d_w_t16);
+  free_dev(m->d_w_final4_half); free_dev(m->d_w_t16);
   free_dev(m->d_w_final4); free_dev(m->d_w_final4_rt); free_dev(m->d_w_final4_split); free_dev(m->d_w_quad); free_dev(m->d_frc); free_dev(m->d_sp); free_dev(m->d_trig);
   if (m->d_runs != nullptr) (void)hipFree(m->d_runs);
   free_dev(m->d_scratch);

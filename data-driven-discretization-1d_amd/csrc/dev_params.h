@@ -29,10 +29,7 @@ constexpr int kInMax = 8;     // widest per-derivative null space (G - rank)
 // rhs_mfma.h::eval_rhs re-creates the NaNs a propagating relu would have passed on (one
 // v_cmp per evaluation; the rest only when a state holds a NaN).
 // 64 relu instructions per wave-evaluation become 32 (profiles/r5_valu_census.txt).
-#ifndef DDD_RELU_CLAMP
-#define DDD_RELU_CLAMP 1   // A/B (profiles/r5_ablation.txt): 0 = one v_max_f32 per element, unscaled weights
-#endif
-constexpr int kReluShift = DDD_RELU_CLAMP ? 64 : 0;
+constexpr int kReluShift = 64;
 
 // Equation ids: include/ddd1d.h enum ddd_equation.
 enum : int {

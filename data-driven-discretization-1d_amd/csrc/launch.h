@@ -30,7 +30,7 @@ void integrate_split_spec(const DevParams& p, const IntegrateArgs& a, int blocks
 template <int kEq>
 void integrate_quad_spec(const DevParams& p, const IntegrateArgs& a, int blocks,
                          hipStream_t stream);
-// nets of up to 16 filters on the block-diagonal tower (rhs_mfma.h HalfTower; one-wave groups,
+// nets of up to 16 filters on 16-channel tiles (rhs_mfma.h Tile16Tower; one-wave groups,
 // float32 state): mfma_half.hip, one unit per equation
 template <int kEq>
 void integrate_half_spec(const DevParams& p, const IntegrateArgs& a, int blocks, hipStream_t stream);

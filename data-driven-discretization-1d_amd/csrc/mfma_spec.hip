@@ -94,9 +94,7 @@ void step_spec<DDD_EQ>(int rows, const DevParams& p, const StepArgs& a, int grou
 // layer's operands per evaluation as before.  profiles/r6_adaptive_gap.txt: with the weights
 // streamed, KS N = 256 ran at the rate of the float64-state run-time kernel (70.8 %), 12
 // points below the resident fixed-step kernel.
-#ifndef DDD_ADAPT256_HOIST
-#define DDD_ADAPT256_HOIST (DDD_EQ >= 2)
-#endif
+constexpr bool kAdapt256Hoist = DDD_EQ >= 2;
 template <>
 void adaptive_spec<DDD_EQ>(int rows, const DevParams& p, const AdaptiveArgs& a, int blocks,
                            hipStream_t stream) {
@@ -104,7 +102,7 @@ void adaptive_spec<DDD_EQ>(int rows, const DevParams& p, const AdaptiveArgs& a, 
     hipLaunchKernelGGL((mfma::adaptive_kernel<64, 64, true, DDD_EQ>), dim3(blocks), dim3(64), 0,
                        stream, p, a);
   else
-    hipLaunchKernelGGL((mfma::adaptive_kernel<256, 64, DDD_ADAPT256_HOIST, DDD_EQ>), dim3(blocks), dim3(256),
+    hipLaunchKernelGGL((mfma::adaptive_kernel<256, 64, kAdapt256Hoist, DDD_EQ>), dim3(blocks), dim3(256),
                        0, stream, p, a);
 }
 

@@ -46,21 +46,7 @@ __device__ __forceinline__ double sample_sum(const DevParams& p, const Lane& ln,
   if (kRows == kWR) {
     // one wavefront, N | 64 (a power of two): xor butterfly inside aligned
     // groups of N lanes; a + b == b + a, so every lane ends with the same bits.
-    // ds_bpermute at (lane ^ m) * 4 directly: __shfl_xor spends nine VALU instructions per
-    // step on its width check and index math (54 per error norm, on lanes the MFMA pipe
-    // shares); here one v_xor per step -- lane ^ m never leaves an aligned group of N > m.
-#if !DDD_ADAPTIVE_BUTTERFLY
     for (int m = 1; m < p.N; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-#endif
-    const int lane4 = ln.lane << 2;
-    for (int m = 1; m < p.N; m <<= 1) {
-      const int src = lane4 ^ (m << 2);
-      const long long bits = __double_as_longlong(v);
-      const int lo = __builtin_amdgcn_ds_bpermute(src, (int)bits);
-      const int hi = __builtin_amdgcn_ds_bpermute(src, (int)(bits >> 32));
-      v += __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-    }
     return v;
   }
   // four-wave groups: `red` aliases Shared::un + Shared::flux (free between two
@@ -145,35 +131,6 @@ struct AdaptiveShared {
 // workgroups 1600 next to Shared<256>)
 static_assert(sizeof(Shared<64>) + sizeof(AdaptiveShared<64>) <= 20 * 1024, "8 groups per CU");
 
-#ifndef DDD_ADAPTIVE_LEAN
-#define DDD_ADAPTIVE_LEAN 0   // A/B (profiles/r4_ablation.txt): bit 0 = 64-row groups lean, bit 1 = 256-row
-#endif
-// eval_rhs's kLean for the adaptive kernels: 1 = output-layer weights and cos / sin table
-// fetched per evaluation (the A/B above), 2 = the table only (two ds_read_b128 from the
-// LDS row padding instead of 12 resident registers: the controller's live values -- state
-// and three stage derivatives in float64 / float32, the next output time -- need them)
-#ifndef DDD_ADAPTIVE_TRIG_LDS
-#define DDD_ADAPTIVE_TRIG_LDS 0   // measured (gpurun_out/r5d): resident 77.7 / 72.1 / 66.4 %, LDS / L2 77.2 / 71.8 / 66.3 %
-#endif
-// A/B switches of round 5's controller slimming (profiles/r5_ablation.txt)
-#ifndef DDD_ADAPTIVE_SHORTCUT
-#define DDD_ADAPTIVE_SHORTCUT 1   // stages 2 / 3 without controller load / store / vote
-#endif
-#ifndef DDD_ADAPTIVE_PREFETCH
-#define DDD_ADAPTIVE_PREFETCH 1   // next output time requested during stage 3
-#endif
-#ifndef DDD_ADAPTIVE_SPECULATE
-#define DDD_ADAPTIVE_SPECULATE 0   // first-stage forcing sums prepared across the error test (round 6):
-                                   // measured neutral (profiles/r6_ablation.txt section 6), off
-#endif
-#ifndef DDD_ADAPTIVE_BUTTERFLY
-#define DDD_ADAPTIVE_BUTTERFLY 1  // ds_bpermute at lane ^ m directly instead of __shfl_xor
-#endif
-template <int kRows>
-constexpr int adaptive_lean() {
-  return ((kRows == 64 ? 1 : 2) & DDD_ADAPTIVE_LEAN) != 0 ? 1 : (DDD_ADAPTIVE_TRIG_LDS ? 2 : 0);
-}
-
 template <int kRows, int kWR, bool kHoist, int kEq, bool kWide = false, class TW = DefaultTower>
 __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW, true>())) void adaptive_kernel(
     DevParams p, AdaptiveArgs a) {
@@ -212,8 +169,7 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW, true>(
   };
   // forcing sums computed outside an evaluation (the first stage of every attempt): the
   // masked first trip of forcing_phase2 where the evaluation keeps the masks resident anyway
-  constexpr bool kMaskedSums = kHoist && kWR == 64 && kEq >= 0 && adaptive_lean<kRows>() != 1 &&
-                               spec_folded(kEq >= 0 ? kEq : 0);
+  constexpr bool kMaskedSums = kHoist && kWR == 64 && kEq >= 0 && spec_folded(kEq >= 0 ? kEq : 0);
 
   // The step-size controllers live in LDS, one per sample of the group: their 7
   // doubles + 4 ints are identical on all lanes of a sample and are touched once
@@ -247,15 +203,6 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW, true>(
   int phase = 0;
   int round = 0;
   bool sums_ready = false;   // res.fk_next already holds the forcing sums of this evaluation
-  // One-wave groups also LOOK AHEAD across the error test (round 6): the FSAL stage's evaluation
-  // prepares the sums of the NEXT attempt's first stage for the time that attempt will have if
-  // this one is accepted with the controller saturated at max_step (the Burgers case: every
-  // attempt) -- checked against the real time once the controller has decided, recomputed when
-  // the guess was wrong (a rejection, a step below max_step).  The same instructions on the
-  // same operands as the sums computed in place: the same bits.
-  constexpr bool kSpeculate = kRows == kWR && DDD_ADAPTIVE_SPECULATE;
-  bool sums_guessed = false;
-  float guess_lane = 0.0f;   // the time this lane's (sample, mode) pair was prepared for
   DDD_ADAPT_TRACE_SETUP;
   for (;;) {
     DDD_ADAPT_STAMP(0);
@@ -278,7 +225,6 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW, true>(
     // of the evaluation before them (as the fixed-step integrators do); the first
     // stage of an attempt cannot: its time depends on the error test.
     const bool ahead = fast_frc && (phase == 2 || phase == 3);
-    bool prepare = ahead;
     float tn_lane = (float)tt;
     if (fast_frc) {
       // the lane's (sample, mode) pair of forcing phase 1 belongs to sample frc_sl of
@@ -293,34 +239,16 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW, true>(
         else if (phase == 3) { ft_now = ft + 0.75 * fh; ft_next = ft + fh; }
         else if (phase == 4) { ft_now = ft + fh; ft_next = ft_now; }
       }
-      if (kSpeculate && sums_guessed) {   // (wave-uniform)
-        const bool wrong = tid < res.frc_pairs && (float)ft_now != guess_lane;
-        sums_ready = __builtin_amdgcn_ballot_w64(wrong) == 0ull;
-        sums_guessed = false;
-      }
       if (!sums_ready)
         res.fk_next = forcing_sums<kRows, kWR, kMaskedSums>(p, sm, res, (float)ft_now, tid);
       tn_lane = (float)ft_next;
-      if (kSpeculate && phase == 4) {
-        // the next attempt of sample frc_sl as Control::advance / begin_step / begin_attempt
-        // will set it up if this one is accepted at h_abs = max_step: t = t_new,
-        // t_new' = min(t + max_step, t_bound), h = t_new' - t; its first stage at t + h / 2
-        const double tp = ctl[frc_sl].t_new;
-        double tq = tp + max_step;
-        if (tq - t_bound > 0.0) tq = t_bound;
-        const double guess = frun ? tp + 0.5 * (tq - tp) : ft;
-        tn_lane = (float)guess;
-        guess_lane = tn_lane;
-        prepare = true;
-        sums_guessed = true;
-      }
     }
     DDD_ADAPT_STAMP(1);
-    const float f = eval_rhs<kRows, kWR, kHoist, kEq, false, kWide, adaptive_lean<kRows>(), TW>(
-        p, sm, a.batch, (float)yy, (float)tt, tn_lane, res, fast_frc, nullptr, nullptr, prepare);
+    const float f = eval_rhs<kRows, kWR, kHoist, kEq, false, kWide, TW>(
+        p, sm, a.batch, (float)yy, (float)tt, tn_lane, res, fast_frc, nullptr, nullptr, ahead);
     sums_ready = ahead;
     DDD_ADAPT_STAMP(2);
-    if (DDD_ADAPTIVE_SHORTCUT && (phase == 2 || phase == 3)) {
+    if (phase == 2 || phase == 3) {
       // Stages 2 and 3 of an attempt change nothing of the controller but the evaluation
       // count, and no sample can finish here: no controller load / unpack / store, no vote
       // (two of every three evaluations).  Stage 3 also requests the next output time: the
@@ -333,10 +261,8 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW, true>(
       } else {
         k2 = f;
         y_new = rk23::new_state(y, k0, k1, k2, ctl[slot].h);
-        if (DDD_ADAPTIVE_PREFETCH) {
-          const int ti = ctl[slot].bits >> 3;
-          te_next = a.times[ti < a.n_times ? ti : a.n_times - 1];
-        }
+        const int ti = ctl[slot].bits >> 3;
+        te_next = a.times[ti < a.n_times ? ti : a.n_times - 1];
         phase = 4;
       }
       if (keeper && run) ctl[slot].nfev += 1;   // (the keeper alone touches this field)
@@ -372,13 +298,6 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW, true>(
       c.begin_step(max_step);
       c.begin_attempt(t_bound);
       phase = 2;
-    } else if (!DDD_ADAPTIVE_SHORTCUT && phase == 2) {
-      k1 = f;
-      phase = 3;
-    } else if (!DDD_ADAPTIVE_SHORTCUT && phase == 3) {
-      k2 = f;
-      y_new = rk23::new_state(y, k0, k1, k2, c.h);
-      phase = 4;
     } else {   // phase 4 (2 and 3: above)
       const float k3 = f;
       const double error_norm =
@@ -386,7 +305,7 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW, true>(
       if (c.status == rk23::RUNNING && c.error_test(error_norm)) {
         // solve_ivp: dense output at every t_eval in (t_old, t_new]
         // (times[c.ti] was requested during stage 3: te_next)
-        double te = DDD_ADAPTIVE_PREFETCH ? te_next : a.times[c.ti < a.n_times ? c.ti : a.n_times - 1];
+        double te = te_next;
         while (c.ti < a.n_times) {
           if (!(te <= c.t_new)) break;
           // (spare rows of a 256-row group follow sample 0's controller: no stores)

@@ -95,7 +95,6 @@ struct Tower {
   static constexpr int kFinK = kK_ * kC + 1;        // 4x4x1 reduction steps of the output layer (+ bias)
   static constexpr int kOperandGroups = kK_ * kC / 4;   // ds_read_b128 per lane in the output layer
   static constexpr bool kDefault = kK_ == 5 && kCB_ == 1;
-  static constexpr bool kHalf = false;              // (HalfTower below)
   static constexpr bool kTile16 = false;            // (Tile16Tower below)
   // 7 taps x 64 filters: the hidden layer runs as a loop over the taps (hidden_layer_rolled);
   // fully unrolled its 896 MFMAs per layer and kernel took > 20 minutes to compile
@@ -103,29 +102,13 @@ struct Tower {
   static_assert(kK_ % 2 == 1 && kK_ >= 3 && kK_ <= 7 && kCB_ >= 1 && kCB_ <= 2, "tower geometry");
 };
 typedef Tower<kKW, 1> DefaultTower;
-// Nets of up to 16 filters (filter_size <= 16, training.py:134-136 leaves it free) in the
-// default tower's layout, BLOCK-DIAGONAL (round 6): embedded with zero weights they occupy a
-// quarter of every 32 x 32 x 2 MFMA of the hidden layer (16 of 32 output rows x 16 of 32
-// reduction channels: 25.7 % of the issued work is the net's).  Here one MFMA pass carries
-// BOTH 32-position tiles of the wavefront: output rows 0..15 = the 16 channels at positions
-// j, rows 16..31 = the same channels at positions 32 + j; reduction half 0 = the 16 input
-// channels at the tap rows of position j, half 1 = those of position 32 + j, the weight
-// panel block-diagonal.  Half the hidden-layer MFMAs (81 instead of 162), and the output
-// layer reduces over 5 x 16 + 1 instead of 5 x 32 + 1 steps.  Every accumulation chain keeps
-// the embedded evaluation's order (the products dropped are exact zeros): the same bits.
-// LDS layout, input layer and everything outside the tower: the default tower's.
-struct HalfTower {
-  static constexpr int kK = kKW, kCB = 1, kC = 32, kHS = 36, kInSteps = 3;
-  static constexpr int kHidK = kKW * 32 / 2, kHidGroups = kHidK / 4;
-  static constexpr int kFinC = 16;
-  static constexpr int kFinK = kKW * kFinC + 1;
-  static constexpr int kOperandGroups = kKW * kFinC / 4;
-  static constexpr bool kDefault = true, kRolled = false, kHalf = true, kTile16 = false;
-};
-// ... and the same nets on 16-CHANNEL TILES (round 6): every layer of the
-// tower on v_mfma_f32_16x16x4_f32 -- D[16 channels][16 positions], four position tiles per
-// wavefront, the reduction four (tap, channel) slots per step: no zero blocks at all
-// (hidden layer: 4 x 21 steps of 32 cycles = 2 688 against the block-diagonal form's 5 184).
+// Nets of up to 16 filters (filter_size <= 16, training.py:134-136 leaves it free): embedded
+// with zero weights in the default tower they would occupy a quarter of every 32 x 32 x 2 MFMA
+// of the hidden layer.  Instead they run on 16-CHANNEL TILES (round 6):
+// every layer of the tower on v_mfma_f32_16x16x4_f32 -- D[16 channels][16 positions], four
+// position tiles per wavefront, the reduction four (tap, channel) slots per step: no zero
+// blocks at all (hidden layer: 4 x 21 steps of 32 cycles = 2 688 against the 5 184 of a
+// block-diagonal 32 x 32 x 2 form, measured and removed: profiles/r6_ablation.txt).
 //   * LDS rows keep 36 floats, channel c at float 4 (c & 3) + (c >> 2): the hidden layer's B
 //     operand of lane (position j, slot sg) is ONE aligned ds_read_b128 per tap -- channels
 //     sg, 4 + sg, 8 + sg, 12 + sg = the lane's slot in steps 4 tap + 0 .. 3, so the chain of
@@ -133,7 +116,7 @@ struct HalfTower {
 //     bits -- and D (lane: channels 4 sg + r) lands with four ds_write_b32 (store_tile16);
 //   * input layer: step 0 = taps 0 .. 3, step 1 = tap 4, bias, 0, 0 (input_layer's k order),
 //     operands by ds_bpermute from the lanes' u / std;
-//   * output layer on the 4x4x1 MFMAs as before (lane == row), its operands four
+//   * output layer on the 4x4x1 MFMAs as in the default tower (lane == row), its operands four
 //     ds_read_b128 per tap row, picked in natural channel order (final_layer4_t16).
 struct Tile16Tower {
   static constexpr int kK = kKW, kCB = 1, kC = 32, kHS = 36, kInSteps = 3;
@@ -141,7 +124,7 @@ struct Tile16Tower {
   static constexpr int kFinC = 16;
   static constexpr int kFinK = kKW * kFinC + 1;
   static constexpr int kOperandGroups = kKW * kFinC / 4;
-  static constexpr bool kDefault = true, kRolled = false, kHalf = false, kTile16 = true;
+  static constexpr bool kDefault = true, kRolled = false, kTile16 = true;
 };
 constexpr int kT16InSteps = 2, kT16HidSteps = 4 * kKW + 1;   // A-operand rows of DevParams::w_quad in this mode
 // floats of one hidden layer in the streamed layout: [group][out block][lane] float4, then the
@@ -158,35 +141,27 @@ __host__ __device__ constexpr int fin4_regs_t(int groups) { return (TW::kFinK * 
 // no cross-wave dependency, wavefronts free-run and eight workgroups share a
 // CU).  Sizes are chosen so that 160 KiB of LDS hold 2 x 256-row or 8 x 64-row
 // workgroups.
-// A/B (profiles/r5_ablation.txt): the one-wave kernels of the 3-tap tower at THREE wavefronts
-// per SIMD (single activation buffer: 11.9 KB of LDS, 168 VGPRs, two resident weight groups)
-// measured below two wavefronts with the whole hidden layer resident (241 VGPRs): 62.9 vs
-// 64.4 % at 4 096 samples, 39.7 vs 50.5 % with one launch per substep.
-// Issue priority by phase (s_setprio; prio_mode(kEq) below).  0: none (rounds 1-5; the
-// run-time-parameterised kernels).  1 (round 5): the matrix layers raised, the VALU phases at 0
-// -- neutral.  2 (round 6): the other way round -- a wavefront's VALU phases (epilogue,
-// forcing, Runge-Kutta update, the adaptive controller) raised, its matrix layers at 0: next
-// to a SIMD partner that streams MFMAs a short VALU burst costs the partner nothing (the
-// matrix pipe is busy with its last MFMA for 64 cycles anyway) and gets this wavefront back to
-// its own MFMAs sooner.  3: as 2, and only the steady middle of the hidden / output layers at
-// 0 -- their first and last operand groups, relu and the activation stores raised as well.
-// Measured (profiles/r6_ablation.txt; fractions of 157.3 TFLOP/s, mode 0 / 2 / 3):
+// The one-wave kernels of the 3-tap tower run at two wavefronts per SIMD with the whole hidden
+// layer resident (241 VGPRs): three wavefronts (single activation buffer, 168 VGPRs, two
+// resident weight groups) measured 62.9 vs 64.4 % at 4 096 samples, 39.7 vs 50.5 % with one
+// launch per substep, and were removed (profiles/r5_ablation.txt).
+// Issue priority by phase (s_setprio; prio_mode(kEq) below).  0: none (the
+// run-time-parameterised kernels).  2: a wavefront's VALU phases (epilogue, forcing,
+// Runge-Kutta update, the adaptive controller) raised, its matrix layers at 0: next to a SIMD
+// partner that streams MFMAs a short VALU burst costs the partner nothing (the matrix pipe is
+// busy with its last MFMA for 64 cycles anyway) and gets this wavefront back to its own MFMAs
+// sooner.  5: as 2, and only the steady middle of the hidden layer at 0 and of the output layer
+// at 1 (its 8-cycle MFMAs ahead of the partner's 64-cycle ones) -- their first and last operand
+// groups, relu and the activation stores raised as well.
+// Measured (profiles/r6_ablation.txt; fractions of 157.3 TFLOP/s, mode 0 / 2 / 5 with the
+// output layer's middle at 0):
 //   KdV N=64 84.3 / 84.7 / 88.0    adaptive KdV 76.0 / 76.4 / 78.6    KS N=256 82.8 / 83.5 / 83.7
 //   Burgers (headline) 82.1 / 81.9 / 81.8    adaptive Burgers 76.4 / 77.0 / 76.7
-// 4 (A/B): 3 with the forcing phases inside the matrix layers at 0 -- no change.  5: 3 with the
-// output layer's middle at 1 instead of 0 (its 8-cycle MFMAs ahead of the partner's 64-cycle
-// ones): KdV 88.4 -> 89.1, KS 84.2 -> 84.4, Burgers unchanged.
+// The output layer's middle at 1: KdV 88.4 -> 89.1, KS 84.2 -> 84.4, Burgers unchanged.  Also
+// measured and removed: the matrix layers raised and the VALU phases at 0 (neutral), the
+// forcing phases inside the matrix layers at 0 (no change).
 // -> per-equation kernels: 5 where the evaluation carries no forcing phases (KdV, KS), 2 in
 //    the Burgers family.
-#ifndef DDD_PRIO_PHASES
-#define DDD_PRIO_PHASES (-1)   // -1: by equation (prio_mode)
-#endif
-#ifndef DDD_K3_WAVES
-#define DDD_K3_WAVES 2
-#endif
-#ifndef DDD_K3_RESIDENT_ALL
-#define DDD_K3_RESIDENT_ALL (DDD_K3_WAVES == 2)
-#endif
 template <int kRows, int kWR = 64, bool kWide = false, class TW = DefaultTower>
 struct Shared {
   static constexpr int kPmMax = kRows;          // (sample, mode) pairs staged
@@ -196,7 +171,7 @@ struct Shared {
   // wavefront execute in order), so the layer can be written in place -- 20 KB instead of
   // 37 KB per group: eight groups per CU = two wavefronts per SIMD instead of one.  hB then
   // only holds the second half of the per-row cos / sin table (four floats per row).
-  static constexpr bool kSingleBuffer = kRows == kWR && (TW::kCB == 2 || (TW::kK == 3 && DDD_K3_WAVES == 3));
+  static constexpr bool kSingleBuffer = kRows == kWR && TW::kCB == 2;
   static constexpr int kHBStride = kSingleBuffer ? 4 : TW::kHS;
   static constexpr int kHBPad = kSingleBuffer ? 0 : TW::kC;      // float offset of a row's padding in hB
   float hA[kRows * TW::kHS];
@@ -280,7 +255,7 @@ __host__ __device__ constexpr bool spec_forced_family(int eq) {
   return eq == EQ_BURGERS || eq == EQ_BURGERS_CONS;
 }
 __host__ __device__ constexpr int prio_mode(int eq) {
-  return DDD_PRIO_PHASES >= 0 ? DDD_PRIO_PHASES : eq < 0 ? 0 : spec_forced_family(eq) ? 2 : 5;
+  return eq < 0 ? 0 : spec_forced_family(eq) ? 2 : 5;
 }
 // Null-space sizes of the accuracy layers at the defaults the specialised
 // kernels assume (polynomial_accuracy_order 1, coefficient_grid_min_size 6;
@@ -519,7 +494,6 @@ __device__ __forceinline__ float fast_tanh(float x) {
 
 __device__ __forceinline__ void activate16(f32x16& acc, int act) {
   if (act == ACT_RELU) {
-#if DDD_RELU_CLAMP
     // TWO elements per instruction: the [0, 1] output clamp of a packed add of zero, on
     // activations that carry the factor 2^-kReluShift (dev_params.h; the host packs the
     // weights accordingly) -- gfx950 has no packed f32 max, and every VALU instruction
@@ -533,18 +507,6 @@ __device__ __forceinline__ void activate16(f32x16& acc, int act) {
       acc[r] = y[0];
       acc[r + 1] = y[1];
     }
-#else
-    // ONE v_max_f32 per element.  fmaxf / fmed3 builtins make the compiler
-    // prepend a canonicalising v_max x, x (it cannot prove an MFMA result is
-    // not a signalling NaN), doubling the VALU work of every layer boundary,
-    // where the matrix pipe is idle; max(0, NaN) = 0 either way.
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      float y;
-      asm("v_max_f32 %0, 0, %1" : "=v"(y) : "v"(acc[r]));
-      acc[r] = y;
-    }
-#endif
   } else if (act == ACT_RELU6) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = fminf(fmaxf(acc[r], 0.0f), 6.0f);
@@ -669,9 +631,7 @@ __device__ __forceinline__ void input_layer(const DevParams& p, const Lane& ln,
 // g + 1 is issued before the four MFMAs of group g (software prefetch).
 // kByteOffsets: `rows` already holds the LDS byte offsets of the operand rows
 // (row * 144 + 64 * half; kept resident by the specialised one-wave integrators).
-// kHalfNet (HalfTower: called with kWR = 32, i.e. ONE tile): the tile's output rows 16..31 are
-// the channels of position 32 + j -- registers 8..15 go to that row.
-template <int kWR, bool kByteOffsets = false, bool kHalfNet = false, int kPrio = 0>
+template <int kWR, bool kByteOffsets = false, int kPrio = 0>
 __device__ __forceinline__ void hidden_layer(const DevParams& p, const Lane& ln,
                                              const float* __restrict__ in,
                                              float* __restrict__ out,
@@ -704,8 +664,8 @@ __device__ __forceinline__ void hidden_layer(const DevParams& p, const Lane& ln,
   __builtin_amdgcn_sched_group_barrier(0x100, kT, 0);     // the reads of group 0
 #pragma unroll
   for (int g = 0; g < 20; ++g) {
-    if (kPrio >= 3 && g == 1) __builtin_amdgcn_s_setprio(0);
-    if (kPrio >= 3 && g == 19) __builtin_amdgcn_s_setprio(3);
+    if (kPrio == 5 && g == 1) __builtin_amdgcn_s_setprio(0);
+    if (kPrio == 5 && g == 19) __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int t = 0; t < kT; ++t) {
       nxt[t] = cur[t];
@@ -732,14 +692,7 @@ __device__ __forceinline__ void hidden_layer(const DevParams& p, const Lane& ln,
 #pragma unroll
   for (int t = 0; t < kT; ++t) {
     activate16(acc[t], act);
-    if constexpr (kHalfNet) {
-      static_assert(kByteOffsets && kT == 1, "block-diagonal nets: one tile, resident offsets");
-      char* orow = reinterpret_cast<char*>(out) + st_off;   // row j, + 16 half
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd)   // registers 4 qd ..: channels (qd & 1) 8 + 4 half + 0..3 of row j + 32 (qd >> 1)
-        *reinterpret_cast<float4*>(orow + (qd >> 1) * 32 * kHS * 4 + 32 * (qd & 1)) = make_float4(
-            acc[t][4 * qd + 0], acc[t][4 * qd + 1], acc[t][4 * qd + 2], acc[t][4 * qd + 3]);
-    } else if (kByteOffsets) store_tile32_at_bytes(out, st_off + t * 32 * kHS * 4, acc[t]);
+    if (kByteOffsets) store_tile32_at_bytes(out, st_off + t * 32 * kHS * 4, acc[t]);
     else store_tile32(out, ln.wave * kWR + t * 32 + j, half, acc[t]);
   }
 }
@@ -779,7 +732,6 @@ __host__ __device__ constexpr int quad_channel_float(int c) {   // position of c
 // relu etc. on one 16x16 tile (4 accumulator registers per lane)
 __device__ __forceinline__ void activate4(f32x4& acc, int act) {
   if (act == ACT_RELU) {
-#if DDD_RELU_CLAMP
 #pragma unroll
     for (int r = 0; r < 4; r += 2) {
       f32x2 v{acc[r], acc[r + 1]}, y;
@@ -787,14 +739,6 @@ __device__ __forceinline__ void activate4(f32x4& acc, int act) {
       acc[r] = y[0];
       acc[r + 1] = y[1];
     }
-#else
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float y;
-      asm("v_max_f32 %0, 0, %1" : "=v"(y) : "v"(acc[r]));
-      acc[r] = y;
-    }
-#endif
   } else {
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[r] = apply_activation(acc[r], act);
@@ -841,7 +785,6 @@ __device__ __forceinline__ void input_layer_quad(const float* __restrict__ un, f
 // hidden layer: this wavefront's 16 output channels x two 16-position tiles.
 // hid_off[t][tap]: byte offset of block (sg & 1, sg >> 1) of the tap's row (the second
 // block, (sg & 1, (sg >> 1) + 2), is 32 bytes on)
-template <int kPrio = 0>
 __device__ __forceinline__ void hidden_layer_quad(const float* __restrict__ in, float* __restrict__ out,
                                                   const float (&w)[kQuadHidSteps],
                                                   const int (&hid_off)[2][kKW], const int (&st_off)[2],
@@ -858,8 +801,6 @@ __device__ __forceinline__ void hidden_layer_quad(const float* __restrict__ in, 
   __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);     // the reads of tap 0
 #pragma unroll
   for (int tap = 0; tap < kKW; ++tap) {
-    if (kPrio >= 3 && tap == 1) __builtin_amdgcn_s_setprio(0);
-    if (kPrio >= 3 && tap == kKW - 1) __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       na[t] = ca[t]; nb[t] = cb[t];
@@ -968,8 +909,8 @@ __device__ __forceinline__ void hidden_layer_t16(const float* __restrict__ in, f
   __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);     // the reads of tap 0
 #pragma unroll
   for (int tap = 0; tap < kKW; ++tap) {
-    if (kPrio >= 3 && tap == 1) __builtin_amdgcn_s_setprio(0);
-    if (kPrio >= 3 && tap == kKW - 1) __builtin_amdgcn_s_setprio(3);
+    if (kPrio == 5 && tap == 1) __builtin_amdgcn_s_setprio(0);
+    if (kPrio == 5 && tap == kKW - 1) __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       nxt[t] = cur[t];
@@ -1105,7 +1046,7 @@ constexpr int kStreamAhead = 2;
 // stream left); the bigger towers: as many groups as the stream runs ahead.
 template <class TW>
 __host__ __device__ constexpr int resident_groups() {
-  return TW::kDefault ? 0 : (TW::kHidGroups * TW::kCB <= 12 && DDD_K3_RESIDENT_ALL ? TW::kHidGroups : kStreamAhead);
+  return TW::kDefault ? 0 : (TW::kHidGroups * TW::kCB <= 12 ? TW::kHidGroups : kStreamAhead);
 }
 constexpr int kResidentQuads = 12;   // float4 registers of Resident::hw
 
@@ -1380,10 +1321,7 @@ __device__ __forceinline__ void load_final4(const DevParams& p, int lane,
   load_rows4<fin4_regs(NG)>(p.w_final4, lane, w);
 }
 
-#ifndef DDD_FIN4_AHEAD
-#define DDD_FIN4_AHEAD 2   // A/B (profiles/r6_ablation.txt)
-#endif
-constexpr int kFin4Ahead = DDD_FIN4_AHEAD;   // operand groups in flight ahead of the MFMAs
+constexpr int kFin4Ahead = 2;   // operand groups in flight ahead of the MFMAs (profiles/r6_ablation.txt)
 
 // (TW: the tower -- K taps x C channels: K C / 4 operand groups of four channels,
 // C / 4 per tap row)
@@ -1424,9 +1362,9 @@ __device__ __forceinline__ void final_layer4(const float* __restrict__ in_f,
   for (int og = 0; og < kFin4Ahead; ++og)
     buf[og] = *reinterpret_cast<const f32x4*>(in + off[og / kPerTap] + 16 * (og % kPerTap));
   __builtin_amdgcn_sched_group_barrier(0x100, kFin4Ahead, 0);
-  if (kPrio >= 3) __builtin_amdgcn_s_setprio(kPrio == 5 ? 1 : 0);   // (5, A/B: the 8-cycle MFMA stream one level up)
+  if (kPrio == 5) __builtin_amdgcn_s_setprio(1);   // (the 8-cycle MFMA stream one level up)
   fin4_run<NG, TW, kAcc>(in, off, w, buf, acc, std::make_integer_sequence<int, TW::kOperandGroups>{});
-  if (kPrio >= 3) __builtin_amdgcn_s_setprio(3);
+  if (kPrio == 5) __builtin_amdgcn_s_setprio(3);
   // bias row: k = K C against a constant 1
   fin4_mfmas<NG, (TW::kFinK - 1) * NG, fin4_regs_t<TW>(NG), kAcc>(
       w, f32x4{1.0f, 1.0f, 1.0f, 1.0f}, acc, std::make_integer_sequence<int, NG>{});
@@ -1434,7 +1372,7 @@ __device__ __forceinline__ void final_layer4(const float* __restrict__ in_f,
 
 // The output layer of Tile16Tower: lane == row as final_layer4, the row's 16 channels stored at
 // float 4 (c & 3) + (c >> 2) -- four ds_read_b128 per tap row, picked in natural channel order.
-// Weights: the 5 x 16 + 1 reduction rows of HalfTower's packing.
+// Weights: 5 x 16 + 1 reduction rows (DevParams::w_final4).
 template <int NG, int kPrio = 0>
 __device__ __forceinline__ void final_layer4_t16(const float* __restrict__ in_f,
                                                  const float (&w)[fin4_regs_t<Tile16Tower>(NG)],
@@ -1446,7 +1384,7 @@ __device__ __forceinline__ void final_layer4_t16(const float* __restrict__ in_f,
 #pragma unroll
   for (int q = 0; q < 4; ++q) cur[q] = *reinterpret_cast<const f32x4*>(in + off[0] + 16 * q);
   __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-  if (kPrio >= 3) __builtin_amdgcn_s_setprio(kPrio == 5 ? 1 : 0);
+  if (kPrio == 5) __builtin_amdgcn_s_setprio(1);
   constexpr int kNW = fin4_regs_t<Tile16Tower>(NG);
   const auto tap_steps = [&](auto tap_c) {
     constexpr int tap = decltype(tap_c)::value;
@@ -1474,7 +1412,7 @@ __device__ __forceinline__ void final_layer4_t16(const float* __restrict__ in_f,
   tap_steps(std::integral_constant<int, 2>{});
   tap_steps(std::integral_constant<int, 3>{});
   tap_steps(std::integral_constant<int, 4>{});
-  if (kPrio >= 3) __builtin_amdgcn_s_setprio(3);
+  if (kPrio == 5) __builtin_amdgcn_s_setprio(3);
   // bias row: k = 80 against a constant 1
   fin4_mfmas<NG, (Tile16Tower::kFinK - 1) * NG, kNW, NG>(
       w, f32x4{1.0f, 1.0f, 1.0f, 1.0f}, acc, std::make_integer_sequence<int, NG>{});
@@ -1482,14 +1420,9 @@ __device__ __forceinline__ void final_layer4_t16(const float* __restrict__ in_f,
 
 // Wavefronts per SIMD the kernels are compiled for: two, except the four-wave groups of the
 // 64-channel towers (158 KB of LDS: one workgroup per CU anyway).
-#ifndef DDD_MIN_WAVES_AB
-#define DDD_MIN_WAVES_AB 2   // A/B (profiles/r4_ablation.txt): 1 = compile every kernel for ONE wavefront per SIMD
-#endif
 template <int kRows, int kWR, class TW, bool kAdaptive = false>
 constexpr int min_waves() {
-  return (TW::kCB == 2 && kRows != kWR) ? 1
-         : (TW::kK == 3 && TW::kCB == 1 && kRows == kWR && !kAdaptive) ? DDD_K3_WAVES
-                                                                      : DDD_MIN_WAVES_AB;
+  return (TW::kCB == 2 && kRows != kWR) ? 1 : 2;
 }
 
 // Kernel-lifetime registers of one lane: hoisted once per launch.
@@ -1518,7 +1451,7 @@ struct Resident {
   float fk_next;            // this lane's harmonic sum for the NEXT evaluation's time
   int frc_run;              // its run of modes: (float offset into Shared::pm) | count << 16
                             // | (index of the sum in Shared::fk) << 24; 0: lane carries none
-  int frc_pairs;            // lanes of forcing phase 1: (samples | batches) x P (wave-uniform)
+  int frc_pairs;            // lanes of forcing phase 1: samples x P (wave-uniform)
   int frc_slot;             // index of this lane's sum in Shared::fk (fixed by the lane, not by
                             // the sample), -1: the lane carries no (sample, k, sin|cos) slot
 #ifdef DDD_PROBES
@@ -1537,8 +1470,8 @@ struct Resident {
 // at the start of the evaluation that uses it.  Inside an evaluation the two
 // phases sit at the input->hidden and hidden->output layer boundaries, where
 // the wavefront otherwise only waits for its activations to land in LDS.
-// (t: per lane -- forcing batches give every batch of lanes its own evaluation time;
-// res.frc_pairs: (samples or batches of the group) x P)
+// (t: per lane -- the lanes of forcing phase 1 may serve another sample of the group than
+// their own; res.frc_pairs: samples of the group x P)
 template <int kRows, int kWR, bool kWide, class TW>
 __device__ __forceinline__ void forcing_phase1(const DevParams& p, Shared<kRows, kWR, kWide, TW>& sm,
                                                const Resident& res, float t, int tid) {
@@ -1602,13 +1535,7 @@ __device__ __forceinline__ float forcing_sums(const DevParams& p, Shared<kRows, 
 // evaluation after this one) at the layer boundaries.
 // ablate / trace: profiling hooks of libddd1d_probe.so (-DDDD_PROBES); every
 // product call site passes the defaults, so they fold away.
-// kLean (adaptive integrators): the output layer's weights and the cos / sin table
-// are NOT kept resident (fetched from L2 / the LDS row padding per evaluation like
-// the run-time kernels do): 31-43 VGPRs the controller state needs.
-// (kLean = 2: only the cos / sin table leaves the registers -- 12 VGPRs for two ds_read_b128
-// per evaluation; the round-5 adaptive kernels)
-template <int kRows, int kWR, bool kHoist, int kEq, bool kTrace, bool kWide, int kLean = 0,
-          class TW = DefaultTower>
+template <int kRows, int kWR, bool kHoist, int kEq, bool kTrace, bool kWide, class TW = DefaultTower>
 __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR, kWide, TW>& sm, int batch,
                                           float u, float t, float t_next, Resident& res,
                                           bool fast_forcing, float* derivs_out,
@@ -1641,10 +1568,6 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
   const bool pow2 = kRows == 64 || (p.N & (p.N - 1)) == 0;   // N | 64: always; else wave-uniform
   constexpr bool kOneWave = kRows == kWR;   // no other wavefront touches this group's LDS
   constexpr int kPrio = prio_mode(kEq);
-#ifndef DDD_QUAD_PRIO
-#define DDD_QUAD_PRIO 0   // A/B: 3 = the four-wavefront groups' hidden layer lowers its steady middle
-#endif
-  constexpr int kQuadPrio = DDD_QUAD_PRIO;
   // output-channel groups of four (final_layer4): the specialised kernels issue
   // their live ones as one compile-time interleaved stream (channels renumbered
   // contiguously, DevParams::w_final4); the run-time-parameterised kernels
@@ -1673,7 +1596,7 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
   constexpr bool kQuad = kSpec && kRows == 64 && kWR == 16 && kHoist;
   static_assert(kWR != 16 || kQuad, "16-row wavefronts: per-equation integrators only");
   constexpr bool kKeepOffsets = (kWR == 64 || kSplit || kQuad) && kHoist;
-  constexpr bool kKeepRows = kKeepOffsets && kEq >= 0 && kLean != 1;
+  constexpr bool kKeepRows = kKeepOffsets && kEq >= 0;
   constexpr bool kKeepPatch = kKeepOffsets && !kWide;   // Resident::pch_idx holds 8 columns
   const int tid = opaque(group_tid<kRows, kWR>());
   const Lane ln = make_lane<kRows, kWR>(p, batch, tid, group < 0 ? (int)blockIdx.x : group);
@@ -1780,11 +1703,10 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
   for (int c = 0; c < kCh; ++c) net[c] = 0.0f;
   if (!fixed) {
     DDD_STAMP(1);
-    // A/B (DDD_PRIO_PHASES): the matrix phases of an evaluation at raised issue priority, the
-    // VALU phases (epilogue, forcing, Runge-Kutta update) at the lowest
-    // (DDD_PRIO_PHASES = 2, round 6: the other way round -- the VALU phases raised, so that a
-    // wavefront's short bookkeeping is not stretched by its SIMD partner's MFMA stream)
-    if (kPrio) __builtin_amdgcn_s_setprio(kPrio == 2 ? 0 : 3);   // (3: stays raised)
+    // issue priority by phase (prio_mode): the VALU phases raised, so that a wavefront's short
+    // bookkeeping is not stretched by its SIMD partner's MFMA stream; the matrix layers at 0
+    // (mode 2), or raised with only their steady middles lowered inside the layers (mode 5)
+    if (kPrio) __builtin_amdgcn_s_setprio(kPrio == 2 ? 0 : 3);
     // kernels that do not keep the hidden layer resident (four-wave adaptive integrators,
     // run-time kernels): the first hidden layer's 81 operand rows are REQUESTED here, before
     // the input layer, its store and the barrier -- one L2 round trip per evaluation that
@@ -1804,17 +1726,13 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
                                                act, res.in_perm, res.st_off);
     }
     const bool frc_next = forced && fast_forcing && prepare_next && !(ablate & 1);
-    if (frc_next) {
-      if (kPrio == 4) __builtin_amdgcn_s_setprio(0);
-      forcing_phase1<kRows, kWR>(p, sm, res, t_next, tid);
-      if (kPrio == 4) __builtin_amdgcn_s_setprio(3);
-    }
+    if (frc_next) forcing_phase1<kRows, kWR>(p, sm, res, t_next, tid);
     float* in = sm.hA;
     float* out = Shared<kRows, kWR, kWide, TW>::kSingleBuffer ? sm.hA : sm.hB;
     for (int l = 1; l < nL - 1; ++l) {
       if constexpr (kQuad) {
         group_barrier<kRows, kWR>();
-        hidden_layer_quad<kQuadPrio>(in, out, res.q_hid, res.q_hid_off, res.q_st_off, act);
+        hidden_layer_quad(in, out, res.q_hid, res.q_hid_off, res.q_st_off, act);
       } else if constexpr (!TW::kDefault) {
         group_barrier<kRows, kWR>();
         if constexpr (TW::kRolled)
@@ -1829,11 +1747,8 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
         group_barrier<kRows, kWR>();
         if constexpr (TW::kTile16) {
           hidden_layer_t16<kPrio>(in, out, res.hid, res.t16_hid_off, res.t16_st_off, act);
-        } else if constexpr (TW::kHalf) {
-          static_assert(kKeepOffsets && kWR == 64 && kOneWave, "block-diagonal nets: resident one-wave integrators");
-          hidden_layer<32, true, true, kPrio>(p, ln, in, out, res.hid, hid_rows, act, res.st_off);
         } else {
-          hidden_layer<kWR, kKeepOffsets, false, kPrio>(p, ln, in, out, res.hid, hid_rows, act, res.st_off);
+          hidden_layer<kWR, kKeepOffsets, kPrio>(p, ln, in, out, res.hid, hid_rows, act, res.st_off);
         }
       }
       float* tmp = in; in = out; out = tmp;
@@ -1937,11 +1852,7 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
       // (masked sums where registers allow: the folded kernels; the unfolded
       // non-flux Burgers kernel needs them for the projection)
       constexpr bool kMaskedSums = kKeepRows && spec_folded(kSpec ? kEq : 0);
-      if (frc_next) {
-        if (kPrio == 4) __builtin_amdgcn_s_setprio(0);
-        res.fk_next = forcing_phase2<kRows, kWR, kMaskedSums>(sm, res);
-        if (kPrio == 4) __builtin_amdgcn_s_setprio(3);
-      }
+      if (frc_next) res.fk_next = forcing_phase2<kRows, kWR, kMaskedSums>(sm, res);
       group_barrier<kRows, kWR>();
       if constexpr (kSpec) {
         f32x4 acc4[kNG];
@@ -2031,7 +1942,7 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
       }
       }   // !kSplit
       DDD_STAMP(3);
-      if (kPrio) __builtin_amdgcn_s_setprio(kPrio >= 2 ? 3 : 0);
+      if (kPrio) __builtin_amdgcn_s_setprio(3);
     }
   } else {
     if (forced && fast_forcing && prepare_next && !(ablate & 1))
@@ -2061,7 +1972,7 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
   // the epilogue, consumed by its last statement
   float4 trig4[kTrigMax / 4];
   if (forced && fast_forcing) {
-    if (kKeepOffsets && kLean == 0) {
+    if (kKeepOffsets) {
       // resident for the launch: lane == grid point never changes
 #pragma unroll
       for (int i = 0; i < kTrigMax / 4; ++i) trig4[i] = res.trig[i];
@@ -2293,7 +2204,7 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
       float total = 0.0f;
 #pragma unroll
       for (int i = 0; i < kTrigMax / 4; ++i) {
-        if (i == 2 && trig_lds && !(kKeepOffsets && kLean == 0)) break;   // entries 8..11 are zero padding
+        if (i == 2 && trig_lds && !kKeepOffsets) break;   // entries 8..11 are zero padding
         const float4 f = fk4[i];
         total = fmaf(f.x, trig4[i].x, total);
         total = fmaf(f.y, trig4[i].y, total);
@@ -2313,8 +2224,7 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
 
 template <int kRows, int kWR, bool kWide, class TW>
 __device__ __forceinline__ void setup_samples(const DevParams& p, Shared<kRows, kWR, kWide, TW>& sm,
-                                              int block, int batch, Resident& res, bool fast,
-                                              int nb = 1);
+                                              int block, int batch, Resident& res, bool fast);
 
 // The forcing of this launch can take the harmonic-sum path (else: per-point sinf).
 template <int kRows, int kWR>
@@ -2324,37 +2234,11 @@ __device__ __forceinline__ bool forcing_is_fast(const DevParams& p) {
          spg * kTrigMax <= Shared<kRows, kWR>::kFkMax && p.P < 256;
 }
 
-// Forcing BATCHES (persistent one-wave integrators, one sample per wavefront): phases 1 and 2
-// of the harmonic sums occupy P = 20 and 2 n_k <= 12 lanes of 64, and every VALU instruction
-// costs the matrix pipe its issue time whatever its lane mask.  With the evaluation times of a
-// fixed-step scheme known in advance, lanes [b P, (b + 1) P) take the time of the (b + 1)-th
-// next evaluation: one pass of phases 1 + 2 in every `nb`-th evaluation serves the next nb
-// (43 instructions per pass: ~14 per evaluation instead of 43).  Every element is computed
-// by the same instructions from the same operands as before -- the same bits as the
-// one-launch-per-substep kernels.  Layout: batch b is "sample slot" b of the staging
-// buffers (Shared::pm set b at entry b P, Shared::fk set b at entry b kTrigMax), exactly
-// where the samples of a multi-sample group sit; phase 3 reads set e mod nb.
-// MEASURED NEUTRAL (profiles/r5_ablation.txt: 82.5 % with and without; 61 GPU tests incl. the
-// bit-for-bit launch-mode comparisons passed with it): phases 1 and 2 already sit in the LDS
-// waits at the layer boundaries, their instructions were not what the matrix pipe waited
-// for.  Off by default; -DDDD_FORCING_BATCH=1 builds it.
-#ifndef DDD_FORCING_BATCH
-#define DDD_FORCING_BATCH 0
-#endif
-constexpr int kForcingBatchMax = 3;
-template <int kRows, int kWR>
-__device__ __forceinline__ int forcing_batches(const DevParams& p) {
-  if (!DDD_FORCING_BATCH || kRows != 64 || kWR != 64 || !forcing_is_fast<kRows, kWR>(p)) return 1;
-  if (2 * p.N <= kRows) return 1;   // more than one sample per wavefront: no spare lanes
-  const int nb = p.P > 0 ? 64 / p.P : 1;
-  return nb > kForcingBatchMax ? kForcingBatchMax : (nb < 1 ? 1 : nb);
-}
-
 // The per-lane loop invariants of the kernels that keep them resident
 // (Resident::fin4_off .. pch_idx): functions of the lane, N and G alone.
 // (Loading them from a per-model table instead -- 115 VALU instructions fewer per
 // launch -- changed nothing measurable: profiles/r3_ablation.txt.)
-template <int kRows, int kWR, bool kHalfNet = false, bool kTile16 = false>
+template <int kRows, int kWR, bool kTile16 = false>
 __device__ __forceinline__ void lane_offsets(const DevParams& p, const Lane& ln, Resident& res) {
   int rows[kKW];
   if constexpr (kTile16) {
@@ -2409,17 +2293,6 @@ __device__ __forceinline__ void lane_offsets(const DevParams& p, const Lane& ln,
     for (int k = 0; k < kKW; ++k)
       res.hid_off[t2][k] = opaque((int)__umul24((unsigned)rows[k], (unsigned)(kHS * 4)) +
                                   64 * half);
-    if constexpr (kHalfNet) {
-      // block-diagonal nets: ONE tile; reduction half h reads channels 0..15 of the tap rows
-      // of position 32 h + j
-      if (t2 == 0) {
-        int rows_h[kKW];
-        tap_rows<kRows == 64>(ln, ln.wave * kWR + ln.lane, p.N, rows_h);   // (lane = 32 half + j)
-#pragma unroll
-        for (int k = 0; k < kKW; ++k)
-          res.hid_off[0][k] = opaque((int)__umul24((unsigned)rows_h[k], (unsigned)(kHS * 4)));
-      }
-    }
     // input layer: taps 0 / 1, taps 2 / 3, tap 4, as byte addresses (one-wave
     // groups: ds_bpermute lane addresses, rows < 64; else into Shared::un)
     res.in_perm[t2][0] = opaque(4 * (half ? rows[1] : rows[0]));
@@ -2439,7 +2312,7 @@ __device__ __forceinline__ void lane_offsets(const DevParams& p, const Lane& ln,
 // Per-launch setup, part 1: resident registers and the tables in LDS.
 template <int kRows, int kWR, bool kHoist, bool kKeepTower = true, bool kWide, class TW>
 __device__ __forceinline__ bool setup_weights(const DevParams& p, Shared<kRows, kWR, kWide, TW>& sm,
-                                              const Lane& ln, Resident& res, int nb = 1) {
+                                              const Lane& ln, Resident& res) {
   constexpr int kThreads = kRows / kWR * 64;
   const int tid = group_tid<kRows, kWR>();
   constexpr int kGW = flavour_stencil(kWide);
@@ -2491,7 +2364,7 @@ __device__ __forceinline__ bool setup_weights(const DevParams& p, Shared<kRows, 
   } else
   if constexpr (TW::kTile16) {
     // A operands of the 16x16x4 layers (DevParams::w_quad in this mode: [2] input rows, [21]
-    // hidden rows of 64 lanes), the output layer's as HalfTower (DevParams::w_final4)
+    // hidden rows of 64 lanes), the output layer's in DevParams::w_final4
     const float* __restrict__ wq = p.w_quad + opaque(ln.lane);
 #pragma unroll
     for (int s2 = 0; s2 < kT16InSteps; ++s2) res.w_in[s2] = wq[s2 * 64];
@@ -2535,8 +2408,7 @@ __device__ __forceinline__ bool setup_weights(const DevParams& p, Shared<kRows, 
   }
   // ---- index math (no memory) ----
   {
-    // (forcing batches, nb > 1: one sample per wavefront, batch b in "sample slot" b)
-    const int spg = nb > 1 ? nb : kRows / p.N;
+    const int spg = kRows / p.N;
     const int sl = row_sample(tid >> 1, p.inv_nk);   // exact
     res.frc_slot = (fast && tid < spg * p.n_k * 2)
                        ? sl * kTrigMax + 2 * ((tid >> 1) - sl * p.n_k) + (tid & 1) : -1;
@@ -2545,7 +2417,7 @@ __device__ __forceinline__ bool setup_weights(const DevParams& p, Shared<kRows, 
   res.fk_off = opaque(ln.sl * kTrigMax * 4);   // (fixed-stencil models with forcing read it too)
   res.st_off = 0;
   if (!p.fixed && !p.linear_taps && kHoist && (kWR == 64 || kWR == 16 || p.w_final4_split != nullptr))
-    lane_offsets<kRows, kWR, TW::kHalf, TW::kTile16>(p, ln, res);
+    lane_offsets<kRows, kWR, TW::kTile16>(p, ln, res);
   // staged (sample, mode) values: zero once, so that reads past a run are finite
   for (int i = tid; i < Shared<kRows, kWR>::kPmMax + 8; i += kThreads)
     sm.pm[i] = make_float2(0.0f, 0.0f);
@@ -2575,10 +2447,9 @@ __device__ __forceinline__ bool setup_weights(const DevParams& p, Shared<kRows, 
 // Per-launch setup of the persistent integrators and the one-group substep kernel.
 template <int kRows, int kWR, bool kHoist, bool kKeepTower = true, bool kWide, class TW>
 __device__ __forceinline__ bool launch_setup(const DevParams& p, Shared<kRows, kWR, kWide, TW>& sm,
-                                             const Lane& ln, int batch, Resident& res,
-                                             int nb = 1) {
-  const bool fast = setup_weights<kRows, kWR, kHoist, kKeepTower>(p, sm, ln, res, nb);
-  setup_samples<kRows, kWR>(p, sm, (int)blockIdx.x, batch, res, fast, nb);
+                                             const Lane& ln, int batch, Resident& res) {
+  const bool fast = setup_weights<kRows, kWR, kHoist, kKeepTower>(p, sm, ln, res);
+  setup_samples<kRows, kWR>(p, sm, (int)blockIdx.x, batch, res, fast);
   return fast;
 }
 
@@ -2597,12 +2468,9 @@ struct SampleSetup {
 
 template <int kRows, int kWR>
 __device__ __forceinline__ SampleSetup fetch_samples(const DevParams& p, int block, int batch,
-                                                     bool fast, int nb = 1) {
+                                                     bool fast) {
   const int tid = group_tid<kRows, kWR>();
   const int spg = kRows / p.N;
-  // forcing batches (nb > 1, spg == 1): "sample slot" b of the staging buffers holds batch b
-  // of the group's ONE sample -- the same index math with nb slots, all reading sample 0
-  const int slots = nb > 1 ? nb : spg;
   SampleSetup s{0.0f, 0.0f, 0.0f, 0, 0, 0};
   if (fast) {   // wave-uniform
     // Both loads are UNCONDITIONAL (lanes without a pair / slot, and samples past
@@ -2612,16 +2480,16 @@ __device__ __forceinline__ SampleSetup fetch_samples(const DevParams& p, int blo
     // its weights is what made the start of a launch cost more than an
     // evaluation (profiles/tools/substep_wave_trace.py).
     const int fsl = row_sample(tid, p.inv_P);   // tid / P, exact
-    const long sample = (long)block * spg + (nb > 1 ? 0 : fsl);
-    const bool has_pair = tid < slots * p.P && sample < batch;
+    const long sample = (long)block * spg + fsl;
+    const bool has_pair = tid < spg * p.P && sample < batch;
     const float4* __restrict__ row = p.frc + (has_pair ? sample * p.P + (tid - fsl * p.P) : 0);
     s.a = row->x; s.omega = row->y; s.phi = row->z;
     // this lane's run of modes [m0, m1): runs[sample][kk] = first (sorted) mode of
     // the sample whose k index is >= kk, precomputed by ddd_set_forcing
     const int sl = row_sample(tid >> 1, p.inv_nk);   // exact
     const int kk = (tid >> 1) - sl * p.n_k;
-    const long sample2 = (long)block * spg + (nb > 1 ? 0 : sl);
-    s.has_slot = tid < slots * p.n_k * 2 && sample2 < batch;
+    const long sample2 = (long)block * spg + sl;
+    s.has_slot = tid < spg * p.n_k * 2 && sample2 < batch;
     const unsigned char* __restrict__ rr = p.runs + (s.has_slot ? sample2 * 8 + kk : 0);
     s.runs_raw = (int)rr[0] | ((int)rr[1] << 8);
     s.run_base = (2 * (sl * p.P) + (tid & 1)) | ((sl * kTrigMax + 2 * kk + (tid & 1)) << 24);
@@ -2651,8 +2519,8 @@ __device__ __forceinline__ void apply_samples(Shared<kRows, kWR, kWide, TW>& sm,
 template <int kRows, int kWR, bool kWide, class TW>
 __device__ __forceinline__ void setup_samples(const DevParams& p, Shared<kRows, kWR, kWide, TW>& sm,
                                               int block, int batch, Resident& res,
-                                              bool fast, int nb) {
-  apply_samples<kRows, kWR>(sm, res, fetch_samples<kRows, kWR>(p, block, batch, fast, nb));
+                                              bool fast) {
+  apply_samples<kRows, kWR>(sm, res, fetch_samples<kRows, kWR>(p, block, batch, fast));
 }
 
 // ---------------------------------------------------------------------------
@@ -2874,9 +2742,7 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW>())) vo
   __shared__ Shared<kRows, kWR, kWide, TW> sm;
   const Lane ln = make_lane<kRows, kWR>(p, a.batch, (int)threadIdx.x, (int)blockIdx.x);
   Resident res;
-  // forcing batches (per-equation kernels: registers to spare; see forcing_batches)
-  const int nb = (kEq >= 0 && kHoist) ? forcing_batches<kRows, kWR>(p) : 1;
-  const bool fast_frc = launch_setup<kRows, kWR, kHoist>(p, sm, ln, a.batch, res, nb);
+  const bool fast_frc = launch_setup<kRows, kWR, kHoist>(p, sm, ln, a.batch, res);
   // (Two wavefronts share each SIMD and run the same phases.  Static priorities
   // by hardware wave slot and start staggering were measured and change nothing
   // (profiles/r2_ablation.txt); the switches survive in the probe build only.)
@@ -2911,23 +2777,9 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW>())) vo
   int until_save = a.save_every;
   size_t snap = 0;
   int evals = 0;
-  // time of the evaluation `ahead` evaluations after stage s of step `step` (ahead >= 0),
-  // in the arithmetic of the loop below; this lane's batch of forcing phase 1
-  const int frc_b = nb > 1 ? row_sample((int)threadIdx.x, p.inv_P) : 0;
-  // (the stage time by an indexed read: one pass in nb evaluations)
-  const auto time_ahead = [&](int step, int s, int ahead) {
-    for (int i = 0; i < ahead; ++i) { if (++s == a.tab.stages) { s = 0; ++step; } }
-    return (float)((a.t0 + (double)step * a.dt) + a.sc.ct[s]);
-  };
-  if (fast_frc && !(ablate & 1)) {
-    float t_lane = (float)(a.t0 + a.tab.c[0] * a.dt);
-    if (nb > 1) {   // batch b: evaluation b of the launch
-      const float t1 = time_ahead(0, 0, 1), t2 = time_ahead(0, 0, 2);
-      t_lane = frc_b == 0 ? t_lane : frc_b == 1 ? t1 : t2;
-    }
-    res.fk_next = forcing_sums<kRows, kWR>(p, sm, res, t_lane, (int)threadIdx.x);
-  }
-  int frc_phase = 0;   // evaluation index mod nb: the set of Shared::fk this evaluation reads
+  if (fast_frc && !(ablate & 1))
+    res.fk_next = forcing_sums<kRows, kWR>(p, sm, res, (float)(a.t0 + a.tab.c[0] * a.dt),
+                                           (int)threadIdx.x);
   // (the per-stage products a[s] h, b[s] h, c[s] dt: StageConsts, formed on the host in this
   // arithmetic -- (ST)a[s] * (ST)dt etc. -- and picked by scalar selects)
   (void)h;
@@ -2950,22 +2802,10 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW>())) vo
       // next step): its forcing sums are prepared inside this evaluation
       const bool last = s + 1 == a.tab.stages;
       const double tn = (last ? t_after : t) + ct.at(last ? 0 : s + 1);
-      float tn_lane = (float)tn;
-      bool prepare = true;
-      if (nb > 1) {
-        // batches: this evaluation reads set frc_phase; the last one of a batch prepares
-        // the next nb evaluations (lanes of batch b: the (b + 1)-th next evaluation)
-        res.fk_off = frc_phase * (kTrigMax * 4);
-        prepare = frc_phase == nb - 1;
-        if (prepare) {
-          const float t2 = time_ahead(step, s, 2), t3 = time_ahead(step, s, 3);
-          tn_lane = frc_b == 0 ? tn_lane : frc_b == 1 ? t2 : t3;
-        }
-        frc_phase = prepare ? 0 : frc_phase + 1;
-      }
+      const float tn_lane = (float)tn;
       const float f = eval_rhs<kRows, kWR, kHoist, kEq, kTrace>(
           p, sm, a.batch, (float)us, (float)(t + ct.at(s)), tn_lane, res, fast_frc,
-          nullptr, nullptr, prepare, -1, ablate, tr);
+          nullptr, nullptr, true, -1, ablate, tr);
       if ((a.sc.b_nonzero >> s) & 1) ynew = ynew + bh.at(s) * (ST)f;
       kprev = f;
     }

@@ -155,10 +155,9 @@ __global__ __launch_bounds__(kThreads) void fixed_substep_kernel(DevParams p, Su
 // thread's points start at a multiple of four, N % 4 == 0: a quad never straddles the
 // periodic wrap) instead of one dword per window entry; (c) four points per thread:
 // small threads, many wavefronts -- the kernel is latency-bound between barriers.
-#ifndef DDD_STEP_QUADS
-#define DDD_STEP_QUADS 1   // measured: 1 -> 6.50e11, 2 -> 4.31e11, 4 -> 3.48e11 grid-point-steps/s (occupancy:
-#endif                     // the kernel is latency-bound between its barriers, profiles/r4_ablation.txt)
-constexpr int kStepQuads = DDD_STEP_QUADS;          // float4 rows per thread
+// float4 rows per thread, measured: 1 -> 6.50e11, 2 -> 4.31e11, 4 -> 3.48e11 grid-point-steps/s
+// (occupancy: the kernel is latency-bound between its barriers, profiles/r4_ablation.txt)
+constexpr int kStepQuads = 1;
 constexpr int kStepPer = 4 * kStepQuads;            // grid points per thread
 constexpr int kStepTile = kThreads * kStepPer;      // grid points per tile
 constexpr int kStepWin = kStepPer + 12;             // window floats: quads [pos0 - 4, pos0 + kStepPer + 8)

@@ -1,6 +1,5 @@
-"""Nets of up to 16 filters on 16-channel tiles (csrc/rhs_mfma.h Tile16Tower -- or, built with
--DDDD_HALF_T16=0, the block-diagonal HalfTower --, round 6; training.py:134-136 leaves
-filter_size free, model.py:455-458 builds whatever it says).  Same bits as the zero-padded
+"""Nets of up to 16 filters on 16-channel tiles (csrc/rhs_mfma.h Tile16Tower, round 6;
+training.py:134-136 leaves filter_size free, model.py:455-458 builds whatever it says).  Same bits as the zero-padded
 embedding in 32 filters (the launch modes and geometries that still use it), oracle parity at
 1e-5, NaN mask of the reference."""
 import numpy as np
