@@ -81,6 +81,24 @@ class DDDTrainArgs(ctypes.Structure):
   ]
 
 
+class DDDVjpArgs(ctypes.Structure):
+  """struct ddd_vjp_args."""
+  _fields_ = [
+      ('struct_size', ctypes.c_int32),
+      ('batch', ctypes.c_int32),
+      ('weights', ctypes.c_void_p),
+      ('nullspace', ctypes.c_void_p),
+      ('bias', ctypes.c_void_p),
+      ('y', ctypes.c_void_p),
+      ('cotangent', ctypes.c_void_p),
+      ('predictions', ctypes.c_void_p),
+      ('grad_y', ctypes.c_void_p),
+      ('grad_weights', ctypes.c_void_p),
+      ('workspace', ctypes.c_void_p),
+      ('workspace_bytes', ctypes.c_size_t),
+  ]
+
+
 class DDDError(RuntimeError):
   """A libddd1d call returned a non-zero status."""
 
@@ -167,6 +185,10 @@ SIGNATURES = {
                                                      ctypes.c_int]),
     'ddd_train_loss_grad': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
                                            ctypes.POINTER(DDDTrainArgs), _V]),
+    'ddd_vjp_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(DDDConfig),
+                                                   ctypes.c_int]),
+    'ddd_result_vjp': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
+                                      ctypes.POINTER(DDDVjpArgs), _V]),
     'ddd_set_kernel': (ctypes.c_int, [_V, ctypes.c_int]),
     'ddd_kernel_name': (ctypes.c_char_p, [_V]),
     'ddd_fma_per_point': (ctypes.c_int64, [_V]),
@@ -421,6 +443,90 @@ def train_loss_grad(cfg, weights, y, labels, baseline, error_floor, coef_abs, co
   args.workspace_bytes = workspace.numel()
   check(lib.ddd_train_loss_grad(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
   return head_means, grad, preds
+
+
+def _check_f32_device(name, tensor, shape):
+  torch = _torch()
+  if (not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float32 or
+      not tensor.is_cuda or not tensor.is_contiguous()):
+    raise ValueError('{} must be a contiguous float32 device tensor'.format(name))
+  if tuple(tensor.shape) != tuple(shape):
+    raise ValueError('{} has shape {}, expected {}'.format(name, tuple(tensor.shape),
+                                                           tuple(shape)))
+
+
+def vjp_num_weights(cfg) -> int:
+  """Floats of the conv weight vector of `cfg` (ddd_model_create layout)."""
+  c_out = 1
+  if cfg.model_target == MODEL_TARGETS['coefficients']:
+    if cfg.polynomial_accuracy_order > 0:
+      c_out = sum(cfg.input_sizes[d] for d in range(cfg.num_derivatives))
+    else:
+      c_out = cfg.num_derivatives * cfg.stencil_size
+  elif cfg.model_target == MODEL_TARGETS['space_derivatives']:
+    c_out = cfg.num_derivatives
+  total = 0
+  for l in range(cfg.num_layers):
+    cin = 1 if l == 0 else cfg.filter_size
+    cout = c_out if l == cfg.num_layers - 1 else cfg.filter_size
+    total += cfg.kernel_size * cin * cout + cout
+  return total
+
+
+def result_vjp(cfg, weights, y, cotangent=None, nullspace=None, bias=None,
+               want_predictions=None, want_grad_y=True, want_grad_weights=True,
+               workspace=None):
+  """ddd_result_vjp: (predictions or None, grad_y or None, grad_weights or None) on the
+  current stream.
+
+  weights (flat, ddd_model_create layout) / y [batch, N] / cotangent [batch, N, H] /
+  nullspace / bias are float32 device tensors.  Without a cotangent only the
+  predictions [batch, N, H] are computed; with one, grad_y [batch, N] and grad_weights
+  (the layout of `weights`) as asked, and the predictions when want_predictions is true
+  (default: only without a cotangent).  `workspace`: a uint8 device tensor of at least
+  ddd_vjp_workspace_bytes bytes, reused across calls when given.  Shapes, dtypes and
+  devices are checked before any device work."""
+  lib = load_library()
+  torch = _torch()
+  if not isinstance(y, torch.Tensor) or y.dim() != 2:
+    raise ValueError('y must be a [batch, N] tensor')
+  batch, heads = int(y.shape[0]), cfg.num_derivatives + 1
+  ws_bytes = lib.ddd_vjp_workspace_bytes(ctypes.byref(cfg), batch)   # the config checks
+  if ws_bytes == 0:
+    check(-1)
+  _check_f32_device('y', y, (batch, cfg.num_points))
+  _check_f32_device('weights', weights, (vjp_num_weights(cfg),))
+  if cotangent is not None:
+    _check_f32_device('cotangent', cotangent, (batch, cfg.num_points, heads))
+  for name, tensor in (('nullspace', nullspace), ('bias', bias)):
+    if tensor is not None:
+      _check_f32_device(name, tensor, tuple(tensor.shape))
+  if want_predictions is None:
+    want_predictions = cotangent is None
+  if cotangent is None:
+    want_grad_y = want_grad_weights = False
+  require_gpu()
+  if workspace is None or workspace.numel() < ws_bytes:
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
+  preds = (torch.empty((batch, cfg.num_points, heads), dtype=torch.float32, device=y.device)
+           if want_predictions else None)
+  grad_y = torch.empty_like(y) if want_grad_y else None
+  grad_w = torch.empty_like(weights) if want_grad_weights else None
+  args = DDDVjpArgs()
+  args.struct_size = ctypes.sizeof(DDDVjpArgs)
+  args.batch = batch
+  args.weights = weights.data_ptr()
+  args.nullspace = None if nullspace is None else nullspace.data_ptr()
+  args.bias = None if bias is None else bias.data_ptr()
+  args.y = y.data_ptr()
+  args.cotangent = None if cotangent is None else cotangent.data_ptr()
+  args.predictions = None if preds is None else preds.data_ptr()
+  args.grad_y = None if grad_y is None else grad_y.data_ptr()
+  args.grad_weights = None if grad_w is None else grad_w.data_ptr()
+  args.workspace = workspace.data_ptr()
+  args.workspace_bytes = workspace.numel()
+  check(lib.ddd_result_vjp(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
+  return preds, grad_y, grad_w
 
 
 def load_probe_library():

@@ -1699,34 +1699,36 @@ int substep_entry(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream) {
 
 
 // ---- training (train.h) ----------------------------------------------------
-// The configuration checks of ddd_train_workspace_bytes / ddd_train_loss_grad and the
-// kernel parameters they imply (everything but the argument pointers).
+// The configuration checks of ddd_train_workspace_bytes / ddd_train_loss_grad (and of
+// ddd_vjp_workspace_bytes / ddd_result_vjp, which admit the same configurations) and the
+// kernel parameters they imply (everything but the argument pointers).  `who` names the
+// entry point in the messages of what is not supported.
 int train_params(const ddd_config* cfg, int batch, ddd::train::TrainParams* tp, int* blocks,
-                 size_t* ws_bytes, size_t* lds_bytes) {
+                 size_t* ws_bytes, size_t* lds_bytes, const char* who = "training") {
   int rc = common_config_checks(cfg);
   if (rc) return rc;
   if (cfg->equation > DDD_EQ_KS_CONSERVATIVE)
     return fail(DDD_ERR_UNSUPPORTED,
-                "training: equation %d (numerical_flux / Godunov equations) is not supported",
+                "%s: equation %d (numerical_flux / Godunov equations) is not supported", who,
                 cfg->equation);
   if (cfg->model_target == DDD_TARGET_FLUX)
-    return fail(DDD_ERR_UNSUPPORTED, "training: model_target 'flux' is not supported");
+    return fail(DDD_ERR_UNSUPPORTED, "%s: model_target 'flux' is not supported", who);
   if (cfg->model_target < DDD_TARGET_COEFFICIENTS || cfg->model_target > DDD_TARGET_FLUX)
     return fail(DDD_ERR_INVALID_ARGUMENT, "unknown model_target %d", cfg->model_target);
   if (cfg->num_layers < 1)
-    return fail(DDD_ERR_UNSUPPORTED, "training: num_layers = %d (a net without conv layers "
-                "has no conv weights to train)", cfg->num_layers);
+    return fail(DDD_ERR_UNSUPPORTED, "%s: num_layers = %d (a net without conv layers "
+                "has no conv weights to train)", who, cfg->num_layers);
   if (cfg->num_layers > DDD_MAX_LAYERS)
-    return fail(DDD_ERR_UNSUPPORTED, "training: num_layers = %d > %d", cfg->num_layers,
+    return fail(DDD_ERR_UNSUPPORTED, "%s: num_layers = %d > %d", who, cfg->num_layers,
                 DDD_MAX_LAYERS);
   if (cfg->kernel_size < 1 || cfg->kernel_size > 7)
-    return fail(DDD_ERR_UNSUPPORTED, "training: kernel_size = %d out of range [1, 7]",
+    return fail(DDD_ERR_UNSUPPORTED, "%s: kernel_size = %d out of range [1, 7]", who,
                 cfg->kernel_size);
   if (cfg->filter_size < 1 || cfg->filter_size > 64)
-    return fail(DDD_ERR_UNSUPPORTED, "training: filter_size = %d out of range [1, 64]",
+    return fail(DDD_ERR_UNSUPPORTED, "%s: filter_size = %d out of range [1, 64]", who,
                 cfg->filter_size);
   if (cfg->num_points < 8 || cfg->num_points > 256)
-    return fail(DDD_ERR_UNSUPPORTED, "training: num_points = %d out of range [8, 256]",
+    return fail(DDD_ERR_UNSUPPORTED, "%s: num_points = %d out of range [8, 256]", who,
                 cfg->num_points);
   if (cfg->activation < DDD_ACT_RELU || cfg->activation > DDD_ACT_ELU)
     return fail(DDD_ERR_INVALID_ARGUMENT, "unknown activation %d", cfg->activation);
@@ -1821,7 +1823,7 @@ int train_params(const ddd_config* cfg, int batch, ddd::train::TrainParams* tp, 
   }
   *lds_bytes = ddd::train::lds_total_floats(p) * sizeof(float);
   if (*lds_bytes > 160 * 1024)
-    return fail(DDD_ERR_UNSUPPORTED, "training: %zu bytes of LDS needed (> 160 KiB)",
+    return fail(DDD_ERR_UNSUPPORTED, "%s: %zu bytes of LDS needed (> 160 KiB)", who,
                 *lds_bytes);
   return DDD_OK;
 }
@@ -2902,6 +2904,63 @@ int ddd_train_loss_grad(const ddd_config* cfg, const ddd_train_args* a, void* st
   p.grad = a->grad;
   p.head_means = a->head_means;
   DDD_HIP(ddd::train::launch_loss_grad(p, blocks, lds, static_cast<hipStream_t>(stream)));
+  return DDD_OK;
+}
+
+size_t ddd_vjp_workspace_bytes(const ddd_config* cfg, int batch) {
+  ddd::train::TrainParams p;
+  int blocks = 0;
+  size_t ws = 0, lds = 0;
+  if (train_params(cfg, batch, &p, &blocks, &ws, &lds, "ddd_result_vjp")) return 0;
+  return ws;
+}
+
+int ddd_result_vjp(const ddd_config* cfg, const ddd_vjp_args* a, void* stream) {
+  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
+  if (a->struct_size != (int32_t)sizeof(ddd_vjp_args))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_vjp_args.struct_size = %d, library expects %d (ABI mismatch)",
+                a->struct_size, (int)sizeof(ddd_vjp_args));
+  ddd::train::VjpParams q;
+  std::memset(&q, 0, sizeof(q));
+  ddd::train::TrainParams& p = q.t;
+  int blocks = 0;
+  size_t ws = 0, lds = 0;
+  int rc = train_params(cfg, a->batch, &p, &blocks, &ws, &lds, "ddd_result_vjp");
+  if (rc) return rc;
+  if (!a->weights || !a->y)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "ddd_result_vjp: weights and y must not be NULL");
+  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
+  if (projected && (!a->nullspace || !a->bias))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_result_vjp: nullspace/bias required for model_target 'coefficients' "
+                "with polynomial_accuracy_order > 0");
+  const bool want_grads = a->grad_y != nullptr || a->grad_weights != nullptr;
+  if (a->cotangent != nullptr && !want_grads)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_result_vjp: a cotangent with grad_y and grad_weights both NULL");
+  if (a->cotangent == nullptr && want_grads)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_result_vjp: grad_y / grad_weights need a cotangent");
+  if (a->cotangent == nullptr && a->predictions == nullptr)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_result_vjp: no cotangent and no predictions: nothing to compute");
+  if (a->workspace == nullptr || a->workspace_bytes < ws)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_result_vjp: workspace of %zu bytes given, ddd_vjp_workspace_bytes = %zu",
+                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws);
+  p.weights = a->weights;
+  p.nullspace = projected ? a->nullspace : nullptr;
+  p.bias = projected ? a->bias : nullptr;
+  p.y = a->y;
+  p.rows = a->batch;
+  p.predictions = a->predictions;
+  p.ws = static_cast<float*>(a->workspace);
+  p.want_grad = a->grad_weights != nullptr ? 1 : 0;
+  p.grad = a->grad_weights;
+  q.cotangent = a->cotangent;
+  q.grad_y = a->grad_y;
+  DDD_HIP(ddd::train::launch_vjp(q, blocks, lds, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }
 

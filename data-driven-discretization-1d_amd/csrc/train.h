@@ -72,5 +72,20 @@ __host__ __device__ inline size_t lds_total_floats(const TrainParams& p) {
 // loss_grad_kernel on `blocks` workgroups, then reduce_kernel (train.hip)
 hipError_t launch_loss_grad(const TrainParams& p, int blocks, size_t lds_bytes, hipStream_t stream);
 
+// The vector-Jacobian product of one model evaluation (ddd_result_vjp, vjp.hip): the
+// forward pass of loss_grad_kernel, then, with a cotangent, its backward pass from that
+// cotangent instead of the loss's, down to the weights and to the state.  Same
+// configurations, workspace and LDS plan as training (the error-term rows hold the
+// space-derivative cotangents and the state gradient).
+struct VjpParams {
+  TrainParams t;           // configuration, weights, y (rows = batch, no sample_index),
+                           // predictions, ws; want_grad / grad = the weight gradient
+  const float* cotangent;  // [batch][N][H] or null: forward only
+  float* grad_y;           // [batch][N] or null
+};
+
+// vjp_kernel on `blocks` workgroups, then (want_grad) the fixed-order slab sum (vjp.hip)
+hipError_t launch_vjp(const VjpParams& q, int blocks, size_t lds_bytes, hipStream_t stream);
+
 }  // namespace train
 }  // namespace ddd

@@ -2,142 +2,10 @@
 // reduction of its partial slabs, launched by ddd_train_loss_grad (capi.hip).
 #include <hip/hip_runtime.h>
 
-#include "train.h"
+#include "train_device.h"
 
 namespace ddd {
 namespace train {
-
-__device__ __forceinline__ int wrap(int i, int n) {
-  i %= n;
-  return i < 0 ? i + n : i;
-}
-
-__device__ __forceinline__ float activation_grad(float z, int act) {
-  switch (act) {
-    case ACT_RELU: return z > 0.0f ? 1.0f : 0.0f;
-    case ACT_RELU6: return (z > 0.0f && z < 6.0f) ? 1.0f : 0.0f;
-    case ACT_TANH: { const float t = tanhf(z); return 1.0f - t * t; }
-    case ACT_SOFTPLUS: return 1.0f / (1.0f + expf(-z));
-    case ACT_ELU: return z > 0.0f ? 1.0f : expf(z);
-    default: return 1.0f;
-  }
-}
-
-// d equation_rhs_or_flux / d derivative d (dev_params.h), at state y and derivatives dv
-__device__ __forceinline__ float rhs_partial(int eq, int d, float y, const float (&dv)[kMaxDerivs],
-                                             float eta) {
-  switch (eq) {
-    case EQ_BURGERS: return d == 0 ? -y : eta;
-    case EQ_BURGERS_CONS: return d == 0 ? dv[0] : -eta;
-    case EQ_KDV: return d == 0 ? -6.0f * y : -1.0f;
-    case EQ_KDV_CONS: return d == 0 ? 6.0f * dv[0] : 1.0f;
-    case EQ_KS: return d == 0 ? -y : -1.0f;
-    case EQ_KS_CONS: return d == 0 ? dv[0] : 1.0f;
-    default: return 0.0f;
-  }
-}
-
-// out[x][co] = bias[co] + sum_k sum_ci in[x + k - K/2][ci] w[k][ci][co]  (periodic), the
-// pre-activation also stored to `z` (global) when non-null, out = act(pre-activation)
-__device__ inline void conv_forward(const TrainParams& p, int l, const float* in, float* out,
-                                    float* z, int act) {
-  const int n = p.N, cin = p.cin[l], cout = p.cout[l], left = p.K / 2;
-  const float* __restrict__ w = p.weights + p.w_off[l];
-  const float* __restrict__ b = w + (size_t)p.K * cin * cout;
-  for (int idx = threadIdx.x; idx < n * cout; idx += kThreads) {
-    const int x = idx / cout, co = idx - x * cout;
-    float acc = 0.0f;
-    for (int k = 0; k < p.K; ++k) {
-      const float* __restrict__ row = in + (size_t)wrap(x + k - left, n) * cin;
-      const float* __restrict__ wk = w + (size_t)k * cin * cout + co;
-      for (int ci = 0; ci < cin; ++ci) acc = fmaf(row[ci], wk[(size_t)ci * cout], acc);
-    }
-    const float pre = acc + b[co];
-    if (z != nullptr) z[idx] = pre;
-    out[idx] = apply_activation(pre, act);
-  }
-}
-
-// ---- the 32 -> 32 layers on v_mfma_f32_32x32x2_f32 (layout checked by
-// ddd_selftest_mfma_layout, ops.h): A[i][k] from lane i + 32 k, B[k][j] from lane j + 32 k,
-// register r of lane l holds D[(r & 3) + 8 (r >> 2) + 4 (l >> 5)][l & 31].  Each of the
-// four wavefronts owns 32-row tiles (forward, backward-data) or taps (weight gradient).
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int mfma_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// conv_forward for a staged layer: in [N][32] -> out / z [N][32]
-__device__ inline void conv_forward_mfma(const TrainParams& p, int l, const float* wl,
-                                         const float* in, float* out, float* z, int act) {
-  const int n = p.N, left = p.K / 2;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, half = lane >> 5;
-  const float* __restrict__ w = wl + p.wl_off[l];
-  const float* __restrict__ b = p.weights + p.w_off[l] + (size_t)p.K * 32 * 32;
-  for (int t = wave; t < n / 32; t += kThreads / 64) {
-    const int x0 = 32 * t;
-    f32x16 acc;
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    for (int k = 0; k < p.K; ++k) {
-      const float* __restrict__ row = in + (size_t)wrap(x0 + i + k - left, n) * 32 + half;
-      const float* __restrict__ wk = w + (size_t)(k * 32 + half) * 32 + i;
-      for (int c = 0; c < 32; c += 2)
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(row[c], wk[c * 32], acc, 0, 0, 0);
-    }
-    const float bias = b[i];
-    for (int r = 0; r < 16; ++r) {
-      const int idx = (x0 + mfma_row(r, half)) * 32 + i;
-      const float pre = acc[r] + bias;
-      if (z != nullptr) z[idx] = pre;
-      out[idx] = apply_activation(pre, act);
-    }
-  }
-}
-
-// d loss / d pre-activation of the layer below a staged layer:
-// ga[y][ci] = sum_k sum_co gz[y - k + K/2][co] w[k][ci][co], times act'(z[y][ci])
-__device__ inline void conv_backward_data_mfma(const TrainParams& p, int l, const float* wl,
-                                               const float* gz, const float* z, float* out) {
-  const int n = p.N, left = p.K / 2;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, half = lane >> 5;
-  const float* __restrict__ w = wl + p.wl_off[l];
-  for (int t = wave; t < n / 32; t += kThreads / 64) {
-    const int y0 = 32 * t;
-    f32x16 acc;
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    for (int k = 0; k < p.K; ++k) {
-      const float* __restrict__ g = gz + (size_t)wrap(y0 + i - k + left, n) * 32 + half;
-      const float* __restrict__ wk = w + (size_t)(k * 32 + i) * 32 + half;
-      for (int c = 0; c < 32; c += 2)
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(g[c], wk[c], acc, 0, 0, 0);
-    }
-    for (int r = 0; r < 16; ++r) {
-      const int idx = (y0 + mfma_row(r, half)) * 32 + i;
-      out[idx] = acc[r] * activation_grad(z[idx], p.act);
-    }
-  }
-}
-
-// weight gradient of a staged layer: gw[k][ci][co] += sum_x a[x + k - K/2][ci] gz[x][co]
-// (one wavefront per tap), gw[K][32][32 + co] (the bias) += sum_x gz[x][co]
-__device__ inline void conv_weight_grad_mfma(const TrainParams& p, const float* a,
-                                             const float* gz, float* gw) {
-  const int n = p.N, left = p.K / 2;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, half = lane >> 5;
-  for (int k = wave; k < p.K; k += kThreads / 64) {
-    f32x16 acc;
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    for (int x = half; x < n; x += 2)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[(size_t)wrap(x + k - left, n) * 32 + i],
-                                                 gz[(size_t)x * 32 + i], acc, 0, 0, 0);
-    float* __restrict__ gk = gw + (size_t)k * 32 * 32;
-    for (int r = 0; r < 16; ++r) gk[mfma_row(r, half) * 32 + i] += acc[r];
-  }
-  for (int co = threadIdx.x; co < 32; co += kThreads) {
-    float acc = 0.0f;
-    for (int x = 0; x < n; ++x) acc += gz[(size_t)x * 32 + co];
-    gw[(size_t)p.K * 32 * 32 + co] += acc;
-  }
-}
 
 __global__ __launch_bounds__(kThreads) void loss_grad_kernel(TrainParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];

@@ -911,6 +911,159 @@ def predict_time_evolution(inputs, model: LearnedStencilModel):
 
 
 # ---------------------------------------------------------------------------
+# differentiable evaluation: torch.autograd over the fused VJP kernel
+# (ddd_result_vjp, csrc/vjp.hip).  The reference's model was one TF graph, so
+# tf.gradients reached the state, any loss and the midpoint unroll of
+# predict_time_evolution (model.py:643-661); these functions give the same reach.
+# ---------------------------------------------------------------------------
+def _vjp_setup(model: LearnedStencilModel):
+  """The ddd_config of the VJP kernel for `model`, after the checks of what the
+  kernel does not carry (NotImplementedError, before any device work)."""
+  if not isinstance(model, LearnedStencilModel):
+    raise TypeError('differentiable evaluation needs a LearnedStencilModel')
+  hp = model.hparams
+  equation_type = equations_lib.equation_type_from_hparams(hp)
+  if equation_type in equations_lib.FLUX_EQUATION_TYPES.values():
+    raise NotImplementedError('differentiable evaluation: numerical_flux (Godunov) '
+                              'equations are not supported')
+  if hp.model_target not in ('coefficients', 'space_derivatives', 'time_derivative'):
+    raise NotImplementedError('differentiable evaluation: model_target {!r} is not '
+                              'supported'.format(hp.model_target))
+  if not 1 <= hp.num_layers <= 8:
+    raise NotImplementedError('differentiable evaluation: num_layers = {} (1 .. 8 are '
+                              'supported)'.format(hp.num_layers))
+  if hp.kernel_size > 7 or hp.filter_size > 64:
+    raise NotImplementedError('differentiable evaluation: kernel_size <= 7 and '
+                              'filter_size <= 64 are supported')
+  n = model.equation.grid.solution_num_points
+  if not 8 <= n <= 256:
+    raise NotImplementedError('differentiable evaluation: num_points = {} out of range '
+                              '[8, 256]'.format(n))
+  if getattr(model, '_vjp_config', None) is None:
+    from . import training   # (training imports this module)
+    model._vjp_config = training._train_config(model)
+  return model._vjp_config
+
+
+def _vjp_tables(model: LearnedStencilModel):
+  """The null spaces and biases of the projection as float32 device vectors (None, None
+  without a projection), uploaded once per model."""
+  if getattr(model, '_vjp_tables_', None) is None:
+    nullspace = bias = None
+    if model.input_sizes:
+      import torch
+      nullspace = torch.as_tensor(np.concatenate(
+          [t.ravel() for t in model.nullspaces]).astype(np.float32), device='cuda')
+      bias = torch.as_tensor(np.concatenate(
+          [t.ravel() for t in model.biases]).astype(np.float32), device='cuda')
+    model._vjp_tables_ = (nullspace, bias)
+  return model._vjp_tables_
+
+
+def model_weights(model: LearnedStencilModel):
+  """The model's conv kernels and biases as one flat float32 host vector in the
+  ddd_model_create layout, the layout of training.Trainer.weights."""
+  return np.concatenate([np.concatenate([w.ravel(), b.ravel()])
+                         for w, b in zip(model.conv_kernels, model.conv_biases)]
+                        ).astype(np.float32)
+
+
+def _check_state_and_weights(inputs, model, weights):
+  import torch
+  n = model.equation.grid.solution_num_points
+  if (not isinstance(inputs, torch.Tensor) or inputs.dtype != torch.float32 or
+      not inputs.is_cuda or not inputs.is_contiguous() or inputs.dim() != 2 or
+      inputs.shape[1] != n):
+    raise ValueError('inputs must be a contiguous float32 device tensor [batch, {}]'
+                     .format(n))
+  size = sum(w.size + b.size for w, b in zip(model.conv_kernels, model.conv_biases))
+  if weights is None:
+    return torch.as_tensor(model_weights(model), device=inputs.device)
+  if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or
+      not weights.is_cuda or not weights.is_contiguous() or tuple(weights.shape) != (size,)):
+    raise ValueError('weights must be a contiguous flat float32 device tensor of {} '
+                     'floats (ddd_model_create layout)'.format(size))
+  return weights
+
+
+_RESULT_FUNCTION = None
+
+
+def _result_function():
+  """The torch.autograd.Function over ddd_result_vjp (built on first use, so that
+  this module imports without torch)."""
+  global _RESULT_FUNCTION
+  if _RESULT_FUNCTION is None:
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class ResultVJP(torch.autograd.Function):
+      """Forward: one forward-only call.  Backward: one VJP call, which recomputes
+      the forward pass inside the kernel from the saved y and weights."""
+
+      @staticmethod
+      def forward(ctx, y, weights, cfg, nullspace, bias):
+        pred, _, _ = _lib.result_vjp(cfg, weights, y, nullspace=nullspace, bias=bias)
+        ctx.save_for_backward(y, weights)
+        ctx.tables = (cfg, nullspace, bias)
+        return pred
+
+      @staticmethod
+      @once_differentiable
+      def backward(ctx, grad):
+        y, weights = ctx.saved_tensors
+        cfg, nullspace, bias = ctx.tables
+        _, grad_y, grad_w = _lib.result_vjp(
+            cfg, weights, y, grad.contiguous(), nullspace=nullspace, bias=bias,
+            want_grad_y=ctx.needs_input_grad[0], want_grad_weights=ctx.needs_input_grad[1])
+        return grad_y, grad_w, None, None, None
+
+    _RESULT_FUNCTION = ResultVJP
+  return _RESULT_FUNCTION
+
+
+def differentiable_result(inputs, model: LearnedStencilModel, weights=None):
+  """predict_result (model.py:664-697) with torch.autograd: [batch, x, channel] =
+  the space derivatives and the equation of motion (no forcing), differentiable with
+  respect to `inputs` and `weights`.
+
+  inputs: float32 device tensor [batch, x].  weights: None (the model's own kernels,
+  a constant) or a flat float32 device tensor in the ddd_model_create layout, e.g.
+  training.Trainer.weights.  Double backward is not supported."""
+  cfg = _vjp_setup(model)
+  weights = _check_state_and_weights(inputs, model, weights)
+  nullspace, bias = _vjp_tables(model)
+  return _result_function().apply(inputs, weights, cfg, nullspace, bias)
+
+
+def differentiable_time_derivative(inputs, model: LearnedStencilModel, weights=None):
+  """predict_time_derivative (model.py:618-640) with torch.autograd: [batch, x]."""
+  return differentiable_result(inputs, model, weights)[..., -1]
+
+
+def differentiable_time_evolution(inputs, model: LearnedStencilModel,
+                                  num_time_steps: Optional[int] = None, weights=None):
+  """predict_time_evolution (model.py:643-661) with torch.autograd: the midpoint rule
+  with equation.time_step over differentiable_time_derivative, [batch, x, T] (the
+  initial state dropped, no forcing).  num_time_steps defaults to
+  hparams.num_time_steps."""
+  import torch
+  _vjp_setup(model)
+  steps = model.hparams.num_time_steps if num_time_steps is None else num_time_steps
+  if steps is None or int(steps) < 1:
+    raise ValueError('num_time_steps must be >= 1, got {}'.format(steps))
+  weights = _check_state_and_weights(inputs, model, weights)
+  dt = model.equation.time_step
+  y, states = inputs, []
+  for _ in range(int(steps)):
+    k1 = differentiable_time_derivative(y, model, weights)
+    k2 = differentiable_time_derivative(y + (0.5 * dt) * k1, model, weights)
+    y = y + dt * k2
+    states.append(y)
+  return torch.stack(states, dim=-1)
+
+
+# ---------------------------------------------------------------------------
 # the training half (model.py:186-410, 664-810): datasets, labels and the loss
 # ---------------------------------------------------------------------------
 def _cat(tensors, axis):

@@ -498,6 +498,45 @@ DDD_API size_t ddd_train_workspace_bytes(const ddd_config* cfg, int batch);
 DDD_API int ddd_train_loss_grad(const ddd_config* cfg, const ddd_train_args* args,
                                 void* stream);
 
+/* ---- differentiable evaluation --------------------------------------------
+ * Replaces: tf.gradients through model.predict_result (model.py:664-697), the
+ * building block of the reference's differentiable time integration
+ * (predict_time_evolution, model.py:643-661).  One model evaluation
+ * [batch][N] -> predictions [batch][N][H] (result_stack order, as
+ * ddd_train_args.predictions: the space derivatives, then the equation of
+ * motion, no forcing) and its vector-Jacobian product: for a cotangent
+ * c [batch][N][H], grad_y = c^T d predictions / d y and grad_weights =
+ * c^T d predictions / d weights (summed over the batch).  Stateless like the
+ * training ABI: the weights are a device vector in the ddd_model_create layout.
+ * Supports exactly the configurations ddd_train_loss_grad supports; the others
+ * return DDD_ERR_UNSUPPORTED before any device work.
+ * Deterministic: grad_y is per sample (a gather, no cross-sample sum);
+ * grad_weights is summed over the batch in fixed-order partial slabs, no
+ * atomics, so equal inputs give bit-identical outputs. */
+typedef struct ddd_vjp_args {
+  int32_t struct_size;   /* = sizeof(ddd_vjp_args), checked */
+  int32_t batch;         /* rows of y */
+  const float* weights;  /* conv weights (ddd_model_create layout, as ddd_train_args) */
+  const float* nullspace; /* as ddd_train_args */
+  const float* bias;     /* as ddd_train_args */
+  const float* y;        /* [batch][N] */
+  const float* cotangent; /* [batch][N][H], or NULL: forward only */
+  float* predictions;    /* out [batch][N][H] or NULL */
+  float* grad_y;         /* out [batch][N] or NULL */
+  float* grad_weights;   /* out, layout of `weights`, or NULL */
+  void* workspace;       /* ddd_vjp_workspace_bytes(cfg, batch) bytes */
+  size_t workspace_bytes;
+} ddd_vjp_args;
+
+/* Bytes of the caller-allocated workspace of ddd_result_vjp for `batch` samples
+ * (partial weight-gradient slabs and per-workgroup scratch); 0 on error. */
+DDD_API size_t ddd_vjp_workspace_bytes(const ddd_config* cfg, int batch);
+/* Without a cotangent: the predictions only (predictions must then be non-NULL,
+ * grad_y and grad_weights NULL).  With one: at least one of grad_y and
+ * grad_weights, and the predictions too when non-NULL.  The forward pass is
+ * recomputed inside the call; nothing is kept between calls. */
+DDD_API int ddd_result_vjp(const ddd_config* cfg, const ddd_vjp_args* args, void* stream);
+
 /* ---- introspection -------------------------------------------------------*/
 DDD_API int ddd_set_kernel(ddd_model* model, int kernel_kind);
 /* "mfma_f32_r64", "mfma_f32_r64w32", "mfma_f32_r64w16" (small ensembles: every 64-row group
