@@ -1,19 +1,25 @@
 #!/usr/bin/env python
 """Headline benchmark: grid-point-steps/s of the learned-stencil integration path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
     (`python bench.py --gpus N` without a torchrun environment re-launches
     itself under torch.distributed.run on 127.0.0.1)
+
+A plain run measures the headline workload alone: set-up, pre-heat, warm-up,
+the timed steps, --dump-outputs, the result line.  Everything else the
+benchmark measures or checks -- the secondary batch, the extra configurations,
+the CPU baseline, the clock samples, and at N > 1 rank 0's solo run, the
+isolated gather and the hash of the gathered ensemble -- runs only with --full.
 
 Workload = BASELINE.json's north_star target configuration: Burgers N=64,
 learned conv-net stencils (3 layers x 32 filters x kernel 5, conservative
 form, polynomial accuracy order 1), batch = 4096 random-phase initial
 conditions PER GPU with per-sample random forcing, fixed-step midpoint rule at
 the equation's time step (the reference's batched integrator,
-model.integrate_ode, model.py:138-159).  BASELINE.json configs[1] (the same
-model at batch 1024) is measured in the same run and reported under
+model.integrate_ode, model.py:138-159).  With --full, BASELINE.json configs[1]
+(the same model at batch 1024) is measured in the same run and reported under
 "secondary".  A "step" is one full Runge-Kutta step of the whole batch; one
 grid-point-step = one grid point advanced by one step.
 Weights are synthetic (Glorot, seeded); inputs are resident in HBM before
@@ -41,7 +47,7 @@ With N > 1 every rank integrates its own shard of the ensemble (weak scaling,
 no communication during stepping) and the final states are all-gathered over
 RCCL inside the timed region (BASELINE.json config 5's "final gather").
 
-At N = 1 the same run also measures, each over its own >= --config-timed-ms
+With --full at N = 1 the same run also measures, each over its own >= --config-timed-ms
 timed region and each with its roofline fraction, the rest of the contract
 (reported under "configs"): BASELINE configs[2] (KdV N=64 B=4096) and
 configs[3] (KS N=256 B=8192), the headline workload with ONE FUSED LAUNCH PER
@@ -51,7 +57,7 @@ streaming kernel (GB/s against the HBM peak), the batch-1
 on-device adaptive RK23 (the reference's production integrator, one controller
 per sample).  With N > 1 the default shard is 8192 samples per GPU
 (BASELINE configs[4]: 65 536 / 8); rank 0 also reports every rank's kernel
-time and the isolated cost of the final gather.
+time and, with --full, the isolated cost of the final gather.
 
 Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for the roofline and
 cpu_baseline definitions.  With --dump-outputs DIR rank 0 also writes the final
@@ -105,8 +111,13 @@ def parse_args(argv=None):
   ap.add_argument('--batch', type=int, default=None,
                   help='samples per GPU; default 4096 at --gpus 1 (north_star target), '
                        '8192 at --gpus > 1 (BASELINE configs[4]: 65 536 / 8)')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure and check everything besides the headline figure: the '
+                       'secondary batch, the extra configurations, the CPU baseline and the '
+                       'clock samples (N = 1), rank 0 alone, the isolated gather and the '
+                       'gathered hash (N > 1); a plain run times the headline workload only')
   ap.add_argument('--secondary-batch', type=int, default=1024,
-                  help='second batch size measured in the same run at N=1 '
+                  help='with --full: second batch size measured in the same run at N=1 '
                        '(BASELINE.json configs[1]); 0 disables')
   ap.add_argument('--num-points', type=int, default=64)
   ap.add_argument('--equation', default='burgers')
@@ -131,10 +142,10 @@ def parse_args(argv=None):
                   help='repeat the K-step job until the timed region lasts this long; 0 (the '
                        'default): the timed region is exactly one job of --steps steps')
   ap.add_argument('--configs', default='all',
-                  help="comma list of the extra measurements at --gpus 1 ('all', 'none', or of "
-                       + ', '.join(CONFIG_NAMES) + ')')
+                  help="with --full: comma list of the extra measurements at --gpus 1 ('all', "
+                       "'none', or of " + ', '.join(CONFIG_NAMES) + ')')
   ap.add_argument('--config-timed-ms', type=float, default=600.0,
-                  help='minimum timed region of each extra measurement')
+                  help='with --full: minimum timed region of each extra measurement')
   ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                   help='collective backend for --gpus > 1: nccl = RCCL over xGMI (the '
                        'measured configuration); gloo stages the gather through host '
@@ -149,7 +160,7 @@ def parse_args(argv=None):
                        '(csrc/libddd1d_<NAME>.so, __graft_entry__.build_hip(variant=NAME)); named '
                        'in config.library, never a headline run')
   ap.add_argument('--cpu-seconds', type=float, default=12.0,
-                  help='budget for the CPU baseline sample (0 disables)')
+                  help='with --full: budget for the CPU baseline sample (0 disables)')
   ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                   help='after the timed region, write what its last job returned (the final '
                        'states) as DIR/<name>.npy; at most {} MB in all, larger outputs as '
@@ -426,9 +437,9 @@ def measure(args, model, y0_host, world, n, batch, sample_clocks=False):
 
   # 1b. N > 1: the SAME per-rank workload on rank 0 ALONE (the other ranks idle at the
   # barrier), so that one invocation yields the 1 -> N point of the weak-scaling curve
-  # even when no separate --gpus 1 run of this shard size exists ("scaling_detail")
+  # even when no separate --gpus 1 run of this shard size exists ("scaling_detail"; --full)
   solo = None
-  if world > 1:
+  if world > 1 and args.full:
     barrier()
     if dist.get_rank() == 0:
       model.integrate_fixed(y0, args.steps, dt=dt, t0=0.0, scheme=args.scheme,
@@ -476,29 +487,32 @@ def measure(args, model, y0_host, world, n, batch, sample_clocks=False):
   per_rank = None
   if world > 1:
     # one line must explain a < N x result: every rank's own wall / kernel time,
-    # and the final gather timed on its own (outside the timed region, after it)
-    gather_ms = []
-    for _ in range(5):
-      barrier()
-      g0 = time.perf_counter()
-      gather_final(0)
-      wait_slot(0)
-      torch.cuda.synchronize()
-      gather_ms.append((time.perf_counter() - g0) * 1e3)
-    mine = torch.tensor([wall * 1e3, kernel_ms, min(gather_ms)], dtype=torch.float64,
-                        device='cpu' if host else 'cuda')
-    everyone = torch.empty(world * 3, dtype=torch.float64, device=mine.device)
+    # and (--full) the final gather timed on its own (outside the timed region, after it)
+    row = [wall * 1e3, kernel_ms]
+    if args.full:
+      gather_ms = []
+      for _ in range(5):
+        barrier()
+        g0 = time.perf_counter()
+        gather_final(0)
+        wait_slot(0)
+        torch.cuda.synchronize()
+        gather_ms.append((time.perf_counter() - g0) * 1e3)
+      row.append(min(gather_ms))
+    mine = torch.tensor(row, dtype=torch.float64, device='cpu' if host else 'cuda')
+    everyone = torch.empty(world * len(row), dtype=torch.float64, device=mine.device)
     dist.all_gather_into_tensor(everyone, mine)
-    table = everyone.cpu().reshape(world, 3)
+    table = everyone.cpu().reshape(world, len(row))
     per_rank = {'wall_ms': [float(v) for v in table[:, 0]],
                 'kernel_ms': [float(v) for v in table[:, 1]],
-                'gather_ms_isolated': [float(v) for v in table[:, 2]],
                 'gather_bytes_per_rank': int(finals[0][0].numel() * finals[0].element_size()),
-                # the gathered ensemble after `steps` steps from y0 (rank slabs in rank
-                # order): equals the single-process run of the same global sample ids
-                'gathered_sha1': hashlib.sha1(
-                    gathers[0].cpu().numpy().tobytes()).hexdigest(),
                 'gathered_shape': list(gathers[0].shape)}
+    if args.full:
+      per_rank.update({
+          'gather_ms_isolated': [float(v) for v in table[:, 2]],
+          # the gathered ensemble after `steps` steps from y0 (rank slabs in rank
+          # order): equals the single-process run of the same global sample ids
+          'gathered_sha1': hashlib.sha1(gathers[0].cpu().numpy().tobytes()).hexdigest()})
     wall, kernel_ms = float(table[:, 0].max()) * 1e-3, float(table[:, 1].max())
   finite = bool(torch.isfinite(finals[0]).all())
   if not finite:
@@ -1132,13 +1146,13 @@ def main():
   dt = eq.time_step
   n = eq.grid.solution_num_points
 
-  m = measure(args, model, y0_host, world, n, batch, sample_clocks=(rank == 0))
+  m = measure(args, model, y0_host, world, n, batch, sample_clocks=(rank == 0 and args.full))
   output = m.pop('output')
   if rank == 0 and args.dump_outputs:
     dump_output(args.dump_outputs, 'final_states', output.cpu().numpy())
   del output
   secondary = None
-  if world == 1 and args.secondary_batch > 0 and args.secondary_batch != batch:
+  if args.full and world == 1 and args.secondary_batch > 0 and args.secondary_batch != batch:
     b2 = args.secondary_batch
     eq2, model2, _, y02 = build_workload(args, rank, b2)
     m2 = measure(args, model2, y02, world, n, b2)
@@ -1154,7 +1168,7 @@ def main():
     }
 
   configs = None
-  if world == 1 and args.configs != 'none':
+  if args.full and world == 1 and args.configs != 'none':
     configs = extra_configs(args, lib, world)
 
   if rank == 0:
@@ -1198,7 +1212,7 @@ def main():
             'finite': m['finite'],
             'debug_options': args.debug_option, 'library': args.library, 'hparams': json.loads(args.hparams or '{}'),
             'preheat_ms': m['preheat_ms'], 'min_timed_ms': args.min_timed_ms,
-            'timed_wall_ms': m['wall'] * 1e3,
+            'timed_wall_ms': m['wall'] * 1e3, 'full': args.full,
         },
         'roofline': s['roofline'],
         'secondary': secondary,
@@ -1210,7 +1224,7 @@ def main():
     if not m['finite']:
       result['invalid'] = 'non-finite state after the timed run'
 
-    if world == 1 and args.cpu_seconds > 0:
+    if args.full and world == 1 and args.cpu_seconds > 0:
       result['cpu_baseline'] = cpu_baseline(model, forcing, y0_host, args.scheme,
                                             dt, args.cpu_seconds)
     else:

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r2matrix
 rm -rf $O; mkdir -p $O
-b() { name=$1; shift; timeout 600 python bench.py "$@" > $O/bench_$name.json 2>/dev/null; }
+b() { name=$1; shift; timeout 600 python bench.py --full "$@" > $O/bench_$name.json 2>/dev/null; }
 b default
 b default_s20 --steps 20 --warmup 5
 b B2048 --batch 2048 --secondary-batch 0 --cpu-seconds 0

@@ -9,15 +9,15 @@ export TMPDIR=/tmp
 O=gpurun_out/r3prof
 rm -rf $O; mkdir -p $O
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 > $O/smoke.txt
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-B="python bench.py --configs none --secondary-batch 0 --cpu-seconds 0"
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+B="python bench.py --full --configs none --secondary-batch 0 --cpu-seconds 0"
 prof() {  # tag, extra rocprofv3 flags..., -- , bench flags
   local tag=$1; shift
   local flags=(); while [ "$1" != "--" ]; do flags+=("$1"); shift; done; shift
   timeout 600 rocprofv3 --kernel-trace "${flags[@]}" --output-format csv -d $O/$tag -o run -- $B "$@" > $O/$tag.log 2>&1
 }
 # kernel stats of the default command (every kernel of the line) and of the headline alone
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o run -- python bench.py --cpu-seconds 0 > $O/stats_default.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o run -- python bench.py --full --cpu-seconds 0 > $O/stats_default.log 2>&1
 prof stats_B4096 --stats -- --warmup 1000
 prof stats_B1024 --stats -- --batch 1024 --warmup 1000
 prof stats_persub --stats -- --launch-mode per_substep --steps 200 --warmup 200 --preheat-ms 50

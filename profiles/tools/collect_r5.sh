@@ -9,15 +9,15 @@ export TMPDIR=/tmp
 O=gpurun_out/r5prof
 rm -rf $O; mkdir -p $O
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 > $O/smoke.txt
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_s20.json 2> $O/bench_driver_s20.err
-B="python bench.py --configs none --secondary-batch 0 --cpu-seconds 0"
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_s20.json 2> $O/bench_driver_s20.err
+B="python bench.py --full --configs none --secondary-batch 0 --cpu-seconds 0"
 prof() {  # tag, extra rocprofv3 flags..., -- , bench flags
   local tag=$1; shift
   local flags=(); while [ "$1" != "--" ]; do flags+=("$1"); shift; done; shift
   timeout 600 rocprofv3 --kernel-trace "${flags[@]}" --output-format csv -d $O/$tag -o run -- $B "$@" > $O/$tag.log 2>&1
 }
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o run -- python bench.py --cpu-seconds 0 > $O/stats_default.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_default -o run -- python bench.py --full --cpu-seconds 0 > $O/stats_default.log 2>&1
 prof stats_B4096 --stats -- --warmup 1000
 prof stats_B1024 --stats -- --batch 1024 --warmup 1000
 prof stats_B256 --stats -- --batch 256 --warmup 1000
@@ -26,7 +26,7 @@ prof stats_k7 --stats -- --hparams '{"kernel_size": 7}' --steps 200 --warmup 200
 prof stats_f64 --stats -- --hparams '{"filter_size": 64}' --steps 200 --warmup 200
 prof stats_stream_step --stats -- --equation kdv --baseline-stencils --launch-mode per_step --batch 262144 --steps 200 --warmup 20 --preheat-ms 50
 prof stats_lean --stats -- --hparams '{"num_layers": 1}' --warmup 1000
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_adaptive -o run -- python bench.py --cpu-seconds 0 --secondary-batch 0 --steps 20 --warmup 5 --min-timed-ms 50 --configs adaptive_rk23,adaptive_ks_n256_b1024,rk_substep_external > $O/stats_adaptive.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_adaptive -o run -- python bench.py --full --cpu-seconds 0 --secondary-batch 0 --steps 20 --warmup 5 --min-timed-ms 50 --configs adaptive_rk23,adaptive_ks_n256_b1024,rk_substep_external > $O/stats_adaptive.log 2>&1
 short="--warmup 0 --preheat-ms 0 --min-timed-ms 0"
 for c in FETCH_SIZE WRITE_SIZE; do
   prof pmc_${c}_B4096 --pmc $c -- --steps 1000 $short

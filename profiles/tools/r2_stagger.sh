@@ -1,4 +1,4 @@
-run() { timeout 300 python bench.py --secondary-batch 0 --cpu-seconds 0 "$@" 2>/dev/null | python -c "
+run() { timeout 300 python bench.py --full --secondary-batch 0 --cpu-seconds 0 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; c=d['config']; print(c['batch_per_gpu'], c['debug_options'], '%.2f TF'%r['achieved'], '%.3f'%r['frac'])"; }
 run

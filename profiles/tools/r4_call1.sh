@@ -8,19 +8,19 @@ rm -rf $O; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q -s > $O/pytest.log 2>&1
 echo "pytest rc=$?" >> $O/pytest.log
 tail -5 $O/pytest.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "bench rc=$?"
 common="--configs none --secondary-batch 0 --cpu-seconds 0 --min-timed-ms 300 --steps 200 --warmup 20"
 for lib in product noslp; do
   L=""; [ $lib = noslp ] && L="--library noslp"
-  python bench.py $common $L > $O/ab_${lib}_headline.json 2>>$O/ab.err
-  python bench.py $common $L --batch 1024 > $O/ab_${lib}_b1024.json 2>>$O/ab.err
-  python bench.py $common $L --equation ks --num-points 256 --batch 8192 > $O/ab_${lib}_ks256.json 2>>$O/ab.err
-  python bench.py $common $L --hparams '{"nonlinearity": "tanh", "num_layers": 4}' > $O/ab_${lib}_rt_tanh4.json 2>>$O/ab.err
-  python bench.py $common $L --hparams '{"model_target": "time_derivative"}' > $O/ab_${lib}_rt_time_head.json 2>>$O/ab.err
-  python bench.py $common $L --hparams '{"num_layers": 4}' > $O/ab_${lib}_rt_relu4.json 2>>$O/ab.err
-  python bench.py $common $L --equation ks --hparams '{"coefficient_grid_min_size": 9}' > $O/ab_${lib}_wide_ks_cgms9.json 2>>$O/ab.err
-  python bench.py $common $L --equation ks --hparams '{"polynomial_accuracy_order": 0}' > $O/ab_${lib}_wide_ks_pao0.json 2>>$O/ab.err
+  python bench.py --full $common $L > $O/ab_${lib}_headline.json 2>>$O/ab.err
+  python bench.py --full $common $L --batch 1024 > $O/ab_${lib}_b1024.json 2>>$O/ab.err
+  python bench.py --full $common $L --equation ks --num-points 256 --batch 8192 > $O/ab_${lib}_ks256.json 2>>$O/ab.err
+  python bench.py --full $common $L --hparams '{"nonlinearity": "tanh", "num_layers": 4}' > $O/ab_${lib}_rt_tanh4.json 2>>$O/ab.err
+  python bench.py --full $common $L --hparams '{"model_target": "time_derivative"}' > $O/ab_${lib}_rt_time_head.json 2>>$O/ab.err
+  python bench.py --full $common $L --hparams '{"num_layers": 4}' > $O/ab_${lib}_rt_relu4.json 2>>$O/ab.err
+  python bench.py --full $common $L --equation ks --hparams '{"coefficient_grid_min_size": 9}' > $O/ab_${lib}_wide_ks_cgms9.json 2>>$O/ab.err
+  python bench.py --full $common $L --equation ks --hparams '{"polynomial_accuracy_order": 0}' > $O/ab_${lib}_wide_ks_pao0.json 2>>$O/ab.err
 done
 python - <<'PY'
 import json, glob

@@ -11,7 +11,7 @@ tail -4 $O/pytest.log
 common="--secondary-batch 0 --cpu-seconds 0 --min-timed-ms 200 --steps 200 --warmup 20"
 for lib in product adnolean; do
   L=""; [ $lib != product ] && L="--library $lib"
-  python bench.py $common $L --configs adaptive_rk23,adaptive_kdv_n64_b4096,adaptive_ks_n256_b1024 > $O/ab_${lib}.json 2>>$O/ab.err
+  python bench.py --full $common $L --configs adaptive_rk23,adaptive_kdv_n64_b4096,adaptive_ks_n256_b1024 > $O/ab_${lib}.json 2>>$O/ab.err
 done
 python - <<'PY'
 import json, glob

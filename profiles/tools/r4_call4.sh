@@ -8,14 +8,14 @@ timeout 900 python -m pytest tests/test_gpu_rhs.py tests/test_gpu_adaptive.py -m
 echo "pytest rc=$?" >> $O/pytest.log
 tail -15 $O/pytest.log
 common="--configs none --secondary-batch 0 --cpu-seconds 0 --min-timed-ms 300 --steps 100 --warmup 20"
-python bench.py $common --hparams '{"kernel_size": 7}' > $O/k7.json 2>>$O/err.log
-python bench.py $common --hparams '{"filter_size": 64}' > $O/f64.json 2>>$O/err.log
-python bench.py $common --hparams '{"filter_size": 64}' --batch 1024 > $O/f64_b1024.json 2>>$O/err.log
-python bench.py $common --hparams '{"kernel_size": 3}' > $O/k3.json 2>>$O/err.log
-python bench.py $common --hparams '{"filter_size": 16}' > $O/f16_embedded.json 2>>$O/err.log
-python bench.py $common --hparams '{"kernel_size": 7}' --equation ks --num-points 256 --batch 2048 > $O/k7_ks256.json 2>>$O/err.log
-python bench.py $common --hparams '{"filter_size": 64}' --equation ks --num-points 256 --batch 1024 > $O/f64_ks256.json 2>>$O/err.log
-python bench.py $common --hparams '{"kernel_size": 7}' --kernel generic --batch 1024 --steps 20 > $O/k7_generic.json 2>>$O/err.log
+python bench.py --full $common --hparams '{"kernel_size": 7}' > $O/k7.json 2>>$O/err.log
+python bench.py --full $common --hparams '{"filter_size": 64}' > $O/f64.json 2>>$O/err.log
+python bench.py --full $common --hparams '{"filter_size": 64}' --batch 1024 > $O/f64_b1024.json 2>>$O/err.log
+python bench.py --full $common --hparams '{"kernel_size": 3}' > $O/k3.json 2>>$O/err.log
+python bench.py --full $common --hparams '{"filter_size": 16}' > $O/f16_embedded.json 2>>$O/err.log
+python bench.py --full $common --hparams '{"kernel_size": 7}' --equation ks --num-points 256 --batch 2048 > $O/k7_ks256.json 2>>$O/err.log
+python bench.py --full $common --hparams '{"filter_size": 64}' --equation ks --num-points 256 --batch 1024 > $O/f64_ks256.json 2>>$O/err.log
+python bench.py --full $common --hparams '{"kernel_size": 7}' --kernel generic --batch 1024 --steps 20 > $O/k7_generic.json 2>>$O/err.log
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob('gpurun_out/r4d/*.json')):

@@ -9,13 +9,13 @@ echo "pytest rc=$?" >> $O/pytest.log
 tail -8 $O/pytest.log
 common="--configs none --secondary-batch 0 --cpu-seconds 0 --min-timed-ms 400 --steps 1000 --warmup 100"
 for b in 256 512 1024; do
-  python bench.py $common --batch $b > $O/split_b$b.json 2>>$O/err.log
-  python bench.py $common --batch $b --kernel mfma64 > $O/onewave_b$b.json 2>>$O/err.log
+  python bench.py --full $common --batch $b > $O/split_b$b.json 2>>$O/err.log
+  python bench.py --full $common --batch $b --kernel mfma64 > $O/onewave_b$b.json 2>>$O/err.log
 done
-python bench.py $common --batch 1024 --equation kdv > $O/split_kdv_b1024.json 2>>$O/err.log
-python bench.py $common --batch 1024 --equation kdv --kernel mfma64 > $O/onewave_kdv_b1024.json 2>>$O/err.log
-python bench.py $common --batch 2048 --num-points 32 > $O/split_n32_b2048.json 2>>$O/err.log
-python bench.py $common --batch 2048 --num-points 32 --kernel mfma64 > $O/onewave_n32_b2048.json 2>>$O/err.log
+python bench.py --full $common --batch 1024 --equation kdv > $O/split_kdv_b1024.json 2>>$O/err.log
+python bench.py --full $common --batch 1024 --equation kdv --kernel mfma64 > $O/onewave_kdv_b1024.json 2>>$O/err.log
+python bench.py --full $common --batch 2048 --num-points 32 > $O/split_n32_b2048.json 2>>$O/err.log
+python bench.py --full $common --batch 2048 --num-points 32 --kernel mfma64 > $O/onewave_n32_b2048.json 2>>$O/err.log
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob('gpurun_out/r4f/*.json')):

@@ -7,10 +7,10 @@ rm -rf $O; mkdir -p $O
 common="--configs none --secondary-batch 0 --cpu-seconds 0 --min-timed-ms 400 --steps 1000 --warmup 100"
 for lib in product onewave; do
   L=""; [ $lib != product ] && L="--library $lib"
-  python bench.py $common $L --batch 1024 > $O/${lib}_b1024.json 2>>$O/err.log
-  python bench.py $common $L --batch 1024 --equation kdv > $O/${lib}_kdv_b1024.json 2>>$O/err.log
-  python bench.py $common $L --batch 4096 > $O/${lib}_b4096.json 2>>$O/err.log
-  python bench.py $common $L --batch 2048 --equation ks --num-points 256 --steps 400 > $O/${lib}_ks256_b2048.json 2>>$O/err.log
+  python bench.py --full $common $L --batch 1024 > $O/${lib}_b1024.json 2>>$O/err.log
+  python bench.py --full $common $L --batch 1024 --equation kdv > $O/${lib}_kdv_b1024.json 2>>$O/err.log
+  python bench.py --full $common $L --batch 4096 > $O/${lib}_b4096.json 2>>$O/err.log
+  python bench.py --full $common $L --batch 2048 --equation ks --num-points 256 --steps 400 > $O/${lib}_ks256_b2048.json 2>>$O/err.log
 done
 python - <<'PY'
 import json, glob

@@ -9,9 +9,9 @@ rm -rf $O; mkdir -p $O
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -2 $O/smoke.txt
 timeout 1200 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1
 echo "pytest rc=$?" >> $O/pytest.log; tail -15 $O/pytest.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -c 300 $O/bench_default.err
-B="python bench.py --secondary-batch 0 --cpu-seconds 0 --steps 20 --warmup 5 --min-timed-ms 50 --preheat-ms 0 --configs adaptive_rk23,adaptive_ks_n256_b1024"
+B="python bench.py --full --secondary-batch 0 --cpu-seconds 0 --steps 20 --warmup 5 --min-timed-ms 50 --preheat-ms 0 --configs adaptive_rk23,adaptive_ks_n256_b1024"
 timeout 600 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $O/pmc_mix1 -o run -- $B > $O/pmc_mix1.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_FLAT SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d $O/pmc_mix2 -o run -- $B > $O/pmc_mix2.log 2>&1
 find $O -name "*_kernel_trace.csv" -size +3M -delete

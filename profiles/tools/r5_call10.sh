@@ -8,12 +8,12 @@ timeout 900 python -m pytest tests/test_gpu_rhs.py tests/test_gpu_adaptive.py te
 echo "tests exit $?" >> $out/tests.log
 tail -5 $out/tests.log
 common="--configs none --secondary-batch 0 --cpu-seconds 0 --min-timed-ms 300 --steps 200 --warmup 20"
-python bench.py $common --hparams '{"kernel_size": 3}' > $out/k3.json 2>$out/err.log
-python bench.py $common --hparams '{"kernel_size": 7}' > $out/k7.json 2>>$out/err.log
-python bench.py $common --hparams '{"filter_size": 64}' > $out/c64.json 2>>$out/err.log
-python bench.py $common --hparams '{"kernel_size": 3, "num_layers": 4}' > $out/k3_l4.json 2>>$out/err.log
-python bench.py $common --launch-mode per_substep --hparams '{"kernel_size": 3}' > $out/k3_persub.json 2>>$out/err.log
-python bench.py $common --equation ks --num-points 256 --batch 4096 --hparams '{"kernel_size": 3}' > $out/k3_ks256.json 2>>$out/err.log
+python bench.py --full $common --hparams '{"kernel_size": 3}' > $out/k3.json 2>$out/err.log
+python bench.py --full $common --hparams '{"kernel_size": 7}' > $out/k7.json 2>>$out/err.log
+python bench.py --full $common --hparams '{"filter_size": 64}' > $out/c64.json 2>>$out/err.log
+python bench.py --full $common --hparams '{"kernel_size": 3, "num_layers": 4}' > $out/k3_l4.json 2>>$out/err.log
+python bench.py --full $common --launch-mode per_substep --hparams '{"kernel_size": 3}' > $out/k3_persub.json 2>>$out/err.log
+python bench.py --full $common --equation ks --num-points 256 --batch 4096 --hparams '{"kernel_size": 3}' > $out/k3_ks256.json 2>>$out/err.log
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob('gpurun_out/r5k/*.json')):

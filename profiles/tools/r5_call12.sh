@@ -8,9 +8,9 @@ timeout 1200 python -m pytest tests/test_gpu_rhs.py tests/test_gpu_adaptive.py -
 echo "tests exit $?" >> $out/tests.log
 tail -5 $out/tests.log
 common="--configs none --secondary-batch 0 --cpu-seconds 0 --min-timed-ms 300 --steps 200 --warmup 20"
-python bench.py $common --hparams '{"kernel_size": 7, "filter_size": 64}' > $out/k7c64.json 2>$out/err.log
-python bench.py $common --equation ks --num-points 256 --batch 2048 --hparams '{"kernel_size": 7, "filter_size": 64}' > $out/k7c64_ks256.json 2>>$out/err.log
-python bench.py $common --hparams '{"kernel_size": 3, "filter_size": 64}' > $out/k3c64_in_5x64.json 2>>$out/err.log
+python bench.py --full $common --hparams '{"kernel_size": 7, "filter_size": 64}' > $out/k7c64.json 2>$out/err.log
+python bench.py --full $common --equation ks --num-points 256 --batch 2048 --hparams '{"kernel_size": 7, "filter_size": 64}' > $out/k7c64_ks256.json 2>>$out/err.log
+python bench.py --full $common --hparams '{"kernel_size": 3, "filter_size": 64}' > $out/k3c64_in_5x64.json 2>>$out/err.log
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob('gpurun_out/r5n/*.json')):

@@ -8,14 +8,14 @@ timeout 900 python -m pytest tests/test_gpu_integrate.py tests/test_gpu_referenc
 echo "tests exit $?" >> $out/tests.log
 tail -4 $out/tests.log
 common="--configs none --secondary-batch 0 --cpu-seconds 0 --min-timed-ms 300 --steps 200 --warmup 20"
-python bench.py $common > $out/persistent.json 2>$out/err.log
-python bench.py $common --launch-mode per_substep > $out/persub_b4096.json 2>>$out/err.log
-python bench.py $common --launch-mode per_step > $out/perstep_b4096.json 2>>$out/err.log
-python bench.py $common --launch-mode per_substep --batch 8192 > $out/persub_b8192.json 2>>$out/err.log
-python bench.py $common --launch-mode per_step --batch 8192 > $out/perstep_b8192.json 2>>$out/err.log
-python bench.py $common --launch-mode per_substep --batch 2048 > $out/persub_b2048.json 2>>$out/err.log
-python bench.py $common --launch-mode per_substep --equation kdv > $out/persub_kdv.json 2>>$out/err.log
-python bench.py $common --launch-mode per_substep --equation ks --num-points 256 --batch 4096 > $out/persub_ks256.json 2>>$out/err.log
+python bench.py --full $common > $out/persistent.json 2>$out/err.log
+python bench.py --full $common --launch-mode per_substep > $out/persub_b4096.json 2>>$out/err.log
+python bench.py --full $common --launch-mode per_step > $out/perstep_b4096.json 2>>$out/err.log
+python bench.py --full $common --launch-mode per_substep --batch 8192 > $out/persub_b8192.json 2>>$out/err.log
+python bench.py --full $common --launch-mode per_step --batch 8192 > $out/perstep_b8192.json 2>>$out/err.log
+python bench.py --full $common --launch-mode per_substep --batch 2048 > $out/persub_b2048.json 2>>$out/err.log
+python bench.py --full $common --launch-mode per_substep --equation kdv > $out/persub_kdv.json 2>>$out/err.log
+python bench.py --full $common --launch-mode per_substep --equation ks --num-points 256 --batch 4096 > $out/persub_ks256.json 2>>$out/err.log
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob('gpurun_out/r5p/*.json')):

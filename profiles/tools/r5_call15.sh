@@ -5,17 +5,17 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 out=gpurun_out/r5q; rm -rf $out; mkdir -p $out
 common="--configs none --secondary-batch 0 --cpu-seconds 0 --min-timed-ms 300 --steps 200 --warmup 20"
-python bench.py $common > $out/headline.json 2>$out/err.log
-python bench.py $common --batch 1024 > $out/b1024.json 2>>$out/err.log
-python bench.py $common --equation kdv > $out/kdv.json 2>>$out/err.log
-python bench.py $common --equation ks --num-points 256 --batch 8192 > $out/ks256.json 2>>$out/err.log
-python bench.py $common --launch-mode per_substep > $out/persub.json 2>>$out/err.log
-python bench.py $common --launch-mode per_step > $out/perstep.json 2>>$out/err.log
-python bench.py $common --hparams '{"kernel_size": 7}' > $out/k7.json 2>>$out/err.log
-python bench.py $common --hparams '{"kernel_size": 3}' > $out/k3.json 2>>$out/err.log
-python bench.py $common --hparams '{"model_target": "time_derivative"}' > $out/time_head.json 2>>$out/err.log
-python bench.py $common --equation ks --hparams '{"coefficient_grid_min_size": 9}' > $out/wide.json 2>>$out/err.log
-python bench.py --cpu-seconds 0 --secondary-batch 0 --steps 20 --warmup 5 --min-timed-ms 50 --configs adaptive_rk23,adaptive_kdv_n64_b4096,adaptive_ks_n256_b1024 > $out/adaptive.json 2>>$out/err.log
+python bench.py --full $common > $out/headline.json 2>$out/err.log
+python bench.py --full $common --batch 1024 > $out/b1024.json 2>>$out/err.log
+python bench.py --full $common --equation kdv > $out/kdv.json 2>>$out/err.log
+python bench.py --full $common --equation ks --num-points 256 --batch 8192 > $out/ks256.json 2>>$out/err.log
+python bench.py --full $common --launch-mode per_substep > $out/persub.json 2>>$out/err.log
+python bench.py --full $common --launch-mode per_step > $out/perstep.json 2>>$out/err.log
+python bench.py --full $common --hparams '{"kernel_size": 7}' > $out/k7.json 2>>$out/err.log
+python bench.py --full $common --hparams '{"kernel_size": 3}' > $out/k3.json 2>>$out/err.log
+python bench.py --full $common --hparams '{"model_target": "time_derivative"}' > $out/time_head.json 2>>$out/err.log
+python bench.py --full $common --equation ks --hparams '{"coefficient_grid_min_size": 9}' > $out/wide.json 2>>$out/err.log
+python bench.py --full --cpu-seconds 0 --secondary-batch 0 --steps 20 --warmup 5 --min-timed-ms 50 --configs adaptive_rk23,adaptive_kdv_n64_b4096,adaptive_ks_n256_b1024 > $out/adaptive.json 2>>$out/err.log
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob('gpurun_out/r5q/*.json')):

@@ -5,12 +5,12 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 out=gpurun_out/r5s; rm -rf $out; mkdir -p $out
 common="--configs none --secondary-batch 0 --cpu-seconds 0 --min-timed-ms 300 --steps 200 --warmup 20"
-python bench.py $common > $out/headline.json 2>$out/err.log
-python bench.py $common --batch 1024 > $out/b1024.json 2>>$out/err.log
-python bench.py $common --scheme bs3 > $out/bs3.json 2>>$out/err.log
-python bench.py $common --scheme rk4 > $out/rk4.json 2>>$out/err.log
-python bench.py $common --non-conservative > $out/plain.json 2>>$out/err.log
-python bench.py $common --state-dtype float64 > $out/f64.json 2>>$out/err.log
+python bench.py --full $common > $out/headline.json 2>$out/err.log
+python bench.py --full $common --batch 1024 > $out/b1024.json 2>>$out/err.log
+python bench.py --full $common --scheme bs3 > $out/bs3.json 2>>$out/err.log
+python bench.py --full $common --scheme rk4 > $out/rk4.json 2>>$out/err.log
+python bench.py --full $common --non-conservative > $out/plain.json 2>>$out/err.log
+python bench.py --full $common --state-dtype float64 > $out/f64.json 2>>$out/err.log
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob('gpurun_out/r5s/*.json')):

@@ -9,7 +9,7 @@ rm -rf $O; mkdir -p $O
 common="--configs none --secondary-batch 0 --cpu-seconds 0 --min-timed-ms 400 --steps 1000 --warmup 100"
 run() {  # tag, flags...
   local tag=$1; shift
-  python bench.py $common "$@" > $O/$tag.json 2>>$O/err.log
+  python bench.py --full $common "$@" > $O/$tag.json 2>>$O/err.log
 }
 run product
 run probe_plain --debug-option prio_split=0

@@ -9,8 +9,8 @@ rm -rf $O; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1
 echo "pytest rc=$?" >> $O/pytest.log; tail -25 $O/pytest.log
 A="--secondary-batch 0 --cpu-seconds 0 --steps 20 --warmup 5 --min-timed-ms 50 --preheat-ms 50 --configs adaptive_rk23,adaptive_kdv_n64_b4096,adaptive_ks_n256_b1024"
-python bench.py $A > $O/adaptive_product.json 2>>$O/err.log
-python bench.py $A --library adtrig0 > $O/adaptive_adtrig0.json 2>>$O/err.log
+python bench.py --full $A > $O/adaptive_product.json 2>>$O/err.log
+python bench.py --full $A --library adtrig0 > $O/adaptive_adtrig0.json 2>>$O/err.log
 python - <<'PY'
 import json
 for tag in ('product', 'adtrig0'):

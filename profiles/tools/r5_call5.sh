@@ -10,7 +10,7 @@ echo "pytest rc=$?" >> $O/pytest.log; tail -12 $O/pytest.log
 A="--secondary-batch 0 --cpu-seconds 0 --steps 20 --warmup 5 --min-timed-ms 50 --preheat-ms 50 --configs adaptive_rk23,adaptive_kdv_n64_b4096,adaptive_ks_n256_b1024"
 for lib in product adnoshort adnopref adnobfly adr4 product; do
   L=""; [ $lib != product ] && L="--library $lib"
-  python bench.py $A $L > $O/adaptive_$lib.json 2>>$O/err.log
+  python bench.py --full $A $L > $O/adaptive_$lib.json 2>>$O/err.log
   python - $lib <<'PY'
 import json, sys
 tag = sys.argv[1]

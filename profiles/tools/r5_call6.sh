@@ -7,7 +7,7 @@ O=gpurun_out/r5f
 rm -rf $O; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1
 echo "pytest rc=$?" >> $O/pytest.log; tail -8 $O/pytest.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python - <<'PY'
 import json
 r = json.load(open('gpurun_out/r5f/bench_default.json'))

@@ -9,12 +9,12 @@ timeout 900 python -m pytest tests/test_gpu_rhs.py tests/test_gpu_ops.py tests/t
 echo "tests exit $?" >> $out/tests.log
 tail -5 $out/tests.log
 common="--configs none --secondary-batch 0 --cpu-seconds 0 --min-timed-ms 300 --steps 200 --warmup 20"
-python bench.py $common --equation ks --hparams '{"coefficient_grid_min_size": 9}' > $out/wide_ks_cgms9.json 2>$out/err.log
-python bench.py $common --equation ks --hparams '{"polynomial_accuracy_order": 0}' > $out/wide_ks_pao0.json 2>>$out/err.log
-python bench.py $common --equation kdv --hparams '{"coefficient_grid_min_size": 10}' > $out/wide_kdv_cgms10.json 2>>$out/err.log
-python bench.py $common --equation burgers --hparams '{"coefficient_grid_min_size": 12}' > $out/wide_burgers_cgms12.json 2>>$out/err.log
-python bench.py $common --equation ks --num-points 256 --batch 4096 --hparams '{"coefficient_grid_min_size": 9}' > $out/wide_ks256_cgms9.json 2>>$out/err.log
-python bench.py $common --hparams '{"model_target": "time_derivative"}' > $out/rt_time_head.json 2>>$out/err.log
+python bench.py --full $common --equation ks --hparams '{"coefficient_grid_min_size": 9}' > $out/wide_ks_cgms9.json 2>$out/err.log
+python bench.py --full $common --equation ks --hparams '{"polynomial_accuracy_order": 0}' > $out/wide_ks_pao0.json 2>>$out/err.log
+python bench.py --full $common --equation kdv --hparams '{"coefficient_grid_min_size": 10}' > $out/wide_kdv_cgms10.json 2>>$out/err.log
+python bench.py --full $common --equation burgers --hparams '{"coefficient_grid_min_size": 12}' > $out/wide_burgers_cgms12.json 2>>$out/err.log
+python bench.py --full $common --equation ks --num-points 256 --batch 4096 --hparams '{"coefficient_grid_min_size": 9}' > $out/wide_ks256_cgms9.json 2>>$out/err.log
+python bench.py --full $common --hparams '{"model_target": "time_derivative"}' > $out/rt_time_head.json 2>>$out/err.log
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob('gpurun_out/r5i/*.json')):

@@ -7,8 +7,8 @@ O=gpurun_out/r6j; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_half_tower.py tests/test_gpu_ring.py -x -q > $O/tests.log 2>&1; tail -15 $O/tests.log
 timeout 900 python -m pytest tests/test_gpu_rhs.py -x -q -k "smaller_towers or nan" > $O/tests2.log 2>&1; tail -3 $O/tests2.log
 L="--cpu-seconds 0 --secondary-batch 1024 --configs adaptive_rk23,kdv_n64_b4096,tower_f16_b4096"
-timeout 600 python bench.py $L > $O/bench_product.json 2> $O/bench_product.err
-timeout 600 python bench.py $L --library prio4 > $O/bench_prio4.json 2> $O/bench_prio4.err
+timeout 600 python bench.py --full $L > $O/bench_product.json 2> $O/bench_product.err
+timeout 600 python bench.py --full $L --library prio4 > $O/bench_prio4.json 2> $O/bench_prio4.err
 python - <<'PY'
 import json
 for tag in ('product', 'prio4'):

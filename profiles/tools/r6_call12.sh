@@ -7,7 +7,7 @@ O=gpurun_out/r6l; mkdir -p $O
 L="--cpu-seconds 0 --secondary-batch 1024 --configs adaptive_rk23,kdv_n64_b4096,ks_n256_b8192,adaptive_kdv_n64_b4096"
 for v in product ahead3 ahead4 prio5 b3 product; do
   if [ $v = product ]; then lib=""; else lib="--library $v"; fi
-  timeout 600 python bench.py $L $lib > $O/bench_$v.json 2> $O/bench_$v.err
+  timeout 600 python bench.py --full $L $lib > $O/bench_$v.json 2> $O/bench_$v.err
   python - $v <<'PY'
 import json, sys
 tag = sys.argv[1]

@@ -7,7 +7,7 @@ O=gpurun_out/r6n; mkdir -p $O
 L="--cpu-seconds 0 --secondary-batch 0 --configs burgers_b256,burgers_b512,adaptive_rk23_b256"
 for v in product q2 q3 product; do
   if [ $v = product ]; then lib=""; else lib="--library $v"; fi
-  timeout 600 python bench.py $L $lib > $O/bench_$v.json 2> $O/bench_$v.err
+  timeout 600 python bench.py --full $L $lib > $O/bench_$v.json 2> $O/bench_$v.err
   python - $v <<'PY'
 import json, sys
 tag = sys.argv[1]

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r6b; rm -rf $O; mkdir -p $O
 ( time timeout 1500 python -m pytest tests -m gpu -q -x --deselect tests/test_gpu_full_size.py > $O/tests.log 2>&1 ) 2> $O/tests.time
 tail -40 $O/tests.log; cat $O/tests.time
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -3 $O/bench_default.err
 python - <<'PY'
 import json

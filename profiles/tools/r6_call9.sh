@@ -7,9 +7,9 @@ export TMPDIR=/tmp
 O=gpurun_out/r6i; mkdir -p $O
 L="--cpu-seconds 0 --secondary-batch 1024 --configs adaptive_rk23,adaptive_kdv_n64_b4096,kdv_n64_b4096,ks_n256_b8192"
 for rep in 1 2; do
-  timeout 600 python bench.py $L --library prio0 > $O/bench_prio0_$rep.json 2> $O/bench_prio0.err
-  timeout 600 python bench.py $L > $O/bench_prio2_$rep.json 2> $O/bench_prio2.err
-  timeout 600 python bench.py $L --library prio3 > $O/bench_prio3_$rep.json 2> $O/bench_prio3.err
+  timeout 600 python bench.py --full $L --library prio0 > $O/bench_prio0_$rep.json 2> $O/bench_prio0.err
+  timeout 600 python bench.py --full $L > $O/bench_prio2_$rep.json 2> $O/bench_prio2.err
+  timeout 600 python bench.py --full $L --library prio3 > $O/bench_prio3_$rep.json 2> $O/bench_prio3.err
 done
 python - <<'PY'
 import json

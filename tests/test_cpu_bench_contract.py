@@ -65,6 +65,20 @@ def test_bench_defaults_match_baseline_config():
   assert bench.PEAK_FP32_TFLOPS == 157.3 and bench.PEAK_HBM_GBPS == 8000.0
 
 
+def test_bench_full_is_opt_in():
+  """A plain run times the headline workload alone; the secondary batch, the extra
+  configurations and the CPU baseline keep their defaults for --full."""
+  bench = _bench()
+  assert bench.parse_args([]).full is False
+  args = bench.parse_args(['--full'])
+  assert args.full is True
+  assert (args.secondary_batch, args.configs, args.cpu_seconds) == (1024, 'all', 12.0)
+  # --full changes nothing about the timed headline workload
+  plain = vars(bench.parse_args(['--steps', '20', '--warmup', '5']))
+  full = vars(bench.parse_args(['--steps', '20', '--warmup', '5', '--full']))
+  assert {k for k in plain if plain[k] != full[k]} == {'full'}
+
+
 def test_bench_rejects_step_counts_it_cannot_time():
   bench = _bench()
   for argv in (['--steps', '0'], ['--warmup', '-1']):

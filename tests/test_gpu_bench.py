@@ -36,3 +36,38 @@ def test_bench_times_exactly_steps_and_dumps_the_final_states(tmp_path):
                                save_every=steps).cpu().numpy()
   assert got.dtype == np.float32 and got.shape == (1, batch, 64)
   np.testing.assert_array_equal(got, want)
+
+
+def _bench_line(argv):
+  out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + argv,
+                       capture_output=True, text=True, timeout=600)
+  assert out.returncode == 0, out.stderr[-3000:]
+  return json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
+
+
+def test_plain_run_measures_the_headline_only():
+  """Without --full the line carries the headline figure and nothing that needs
+  runs of its own: no secondary batch, no extra configurations, no CPU baseline,
+  no clock samples."""
+  result = _bench_line(['--gpus', '1', '--steps', '7', '--warmup', '2', '--batch', '256',
+                        '--preheat-ms', '10'])
+  assert result['steps'] == 7 and result['reps'] == 1 and result['config']['finite']
+  assert result['value'] > 0 and result['ms_per_step'] > 0
+  assert result['config']['full'] is False
+  for key in ('secondary', 'configs', 'cpu_baseline', 'clocks'):
+    assert result[key] is None, key
+  assert result['roofline']['kernel_ms_per_launch'] > 0
+
+
+def test_full_run_keeps_the_extras():
+  """--full adds the secondary batch, the chosen extra configurations and the
+  CPU baseline to the same line."""
+  result = _bench_line(['--gpus', '1', '--steps', '7', '--warmup', '2', '--batch', '256',
+                        '--preheat-ms', '10', '--full', '--secondary-batch', '128',
+                        '--configs', 'kdv_n64_b4096', '--config-timed-ms', '20',
+                        '--cpu-seconds', '0.5'])
+  assert result['config']['full'] is True and result['config']['finite']
+  assert result['secondary']['batch_per_gpu'] == 128 and result['secondary']['value'] > 0
+  kdv = result['configs']['kdv_n64_b4096']
+  assert 'error' not in kdv and kdv['value'] > 0 and kdv['finite']
+  assert result['cpu_baseline']['value'] > 0

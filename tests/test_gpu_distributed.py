@@ -117,7 +117,8 @@ def test_bench_two_ranks_on_this_box():
          if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
   out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
                         '--backend', 'gloo', '--steps', '20', '--warmup', '5', '--batch', '512',
-                        '--preheat-ms', '20', '--min-timed-ms', '5', '--cpu-seconds', '0'],
+                        '--preheat-ms', '20', '--min-timed-ms', '5', '--cpu-seconds', '0',
+                        '--full'],
                        env=env, capture_output=True, text=True, timeout=900)
   assert out.returncode == 0, out.stderr[-3000:]
   line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]
@@ -146,8 +147,8 @@ def test_bench_four_ranks_on_this_box():
   out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '4',
                         '--backend', 'gloo', '--batch', '64', '--steps', '5', '--warmup', '2',
                         '--preheat-ms', '10', '--min-timed-ms', '5', '--configs', 'none',
-                        '--cpu-seconds', '0'], env=env, capture_output=True, text=True,
-                       timeout=1200)
+                        '--cpu-seconds', '0', '--full'], env=env, capture_output=True,
+                       text=True, timeout=1200)
   assert out.returncode == 0, out.stderr[-3000:]
   line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]
   result = json.loads(line)
