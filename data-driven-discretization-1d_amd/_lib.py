@@ -81,6 +81,36 @@ class DDDTrainArgs(ctypes.Structure):
   ]
 
 
+MAX_TIME_STEPS = 8   # DDD_MAX_TIME_STEPS
+MAX_UNROLLED_HEADS = MAX_HEADS + MAX_TIME_STEPS
+
+
+class DDDTrainUnrolledArgs(ctypes.Structure):
+  """struct ddd_train_unrolled_args."""
+  _fields_ = [
+      ('struct_size', ctypes.c_int32),
+      ('batch', ctypes.c_int32),
+      ('num_rows', ctypes.c_int32),
+      ('num_time_steps', ctypes.c_int32),
+      ('weights', ctypes.c_void_p),
+      ('nullspace', ctypes.c_void_p),
+      ('bias', ctypes.c_void_p),
+      ('y', ctypes.c_void_p),
+      ('sample_index', ctypes.c_void_p),
+      ('labels', ctypes.c_void_p),
+      ('baseline', ctypes.c_void_p),
+      ('time_step', ctypes.c_float),
+      ('error_floor', ctypes.c_float * MAX_UNROLLED_HEADS),
+      ('coef_abs', ctypes.c_float * MAX_UNROLLED_HEADS),
+      ('coef_rel', ctypes.c_float * MAX_UNROLLED_HEADS),
+      ('head_means', ctypes.c_void_p),
+      ('grad', ctypes.c_void_p),
+      ('predictions', ctypes.c_void_p),
+      ('workspace', ctypes.c_void_p),
+      ('workspace_bytes', ctypes.c_size_t),
+  ]
+
+
 class DDDVjpArgs(ctypes.Structure):
   """struct ddd_vjp_args."""
   _fields_ = [
@@ -185,6 +215,11 @@ SIGNATURES = {
                                                      ctypes.c_int]),
     'ddd_train_loss_grad': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
                                            ctypes.POINTER(DDDTrainArgs), _V]),
+    'ddd_train_unrolled_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(DDDConfig),
+                                                              ctypes.c_int, ctypes.c_int]),
+    'ddd_train_unrolled_loss_grad': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
+                                                    ctypes.POINTER(DDDTrainUnrolledArgs),
+                                                    _V]),
     'ddd_vjp_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(DDDConfig),
                                                    ctypes.c_int]),
     'ddd_result_vjp': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
@@ -442,6 +477,68 @@ def train_loss_grad(cfg, weights, y, labels, baseline, error_floor, coef_abs, co
   args.workspace = workspace.data_ptr()
   args.workspace_bytes = workspace.numel()
   check(lib.ddd_train_loss_grad(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
+  return head_means, grad, preds
+
+
+def train_unrolled_loss_grad(cfg, weights, y, labels, baseline, error_floor, coef_abs,
+                             coef_rel, num_time_steps, time_step, nullspace=None, bias=None,
+                             sample_index=None, batch=None, want_grad=True,
+                             want_predictions=False, workspace=None):
+  """ddd_train_unrolled_loss_grad: (head_means [2, H'], grad or None, predictions or
+  None) with H' = num_derivatives + 1 + num_time_steps heads; the other arguments as
+  train_loss_grad, labels / baseline [S, N, H'], error_floor / coef_* H' host floats."""
+  lib = load_library()
+  torch = require_gpu()
+  steps = int(num_time_steps)
+  if batch is None:
+    batch = int(sample_index.shape[0]) if sample_index is not None else int(y.shape[0])
+  heads = int(labels.shape[-1])
+  if heads != cfg.num_derivatives + 1 + steps:
+    raise ValueError('labels must have num_derivatives + 1 + num_time_steps = {} channels, '
+                     'got {}'.format(cfg.num_derivatives + 1 + steps, heads))
+  if (y.dim() != 2 or tuple(labels.shape) != tuple(y.shape) + (heads,) or
+      tuple(baseline.shape) != tuple(labels.shape) or y.shape[1] != cfg.num_points):
+    raise ValueError("expected y [S, N], labels / baseline [S, N, H']")
+  if sample_index is not None and (sample_index.dim() != 1 or
+                                   int(sample_index.shape[0]) != batch):
+    raise ValueError('sample_index must have `batch` entries')
+  ws_bytes = lib.ddd_train_unrolled_workspace_bytes(ctypes.byref(cfg), int(batch), steps)
+  if ws_bytes == 0:
+    check(-1)
+  if workspace is None or workspace.numel() < ws_bytes:
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
+  head_means = torch.empty((2, heads), dtype=torch.float32, device=y.device)
+  grad = torch.empty_like(weights) if want_grad else None
+  preds = (torch.empty((batch, y.shape[1], heads), dtype=torch.float32, device=y.device)
+           if want_predictions else None)
+  args = DDDTrainUnrolledArgs()
+  args.struct_size = ctypes.sizeof(DDDTrainUnrolledArgs)
+  args.batch = int(batch)
+  args.num_rows = int(y.shape[0])
+  args.num_time_steps = steps
+  args.time_step = float(time_step)
+  for name, tensor in (('weights', weights), ('y', y), ('labels', labels),
+                       ('baseline', baseline)):
+    if tensor.dtype != torch.float32 or not tensor.is_contiguous() or not tensor.is_cuda:
+      raise ValueError('{} must be a contiguous float32 device tensor'.format(name))
+    setattr(args, name, tensor.data_ptr())
+  args.nullspace = None if nullspace is None else nullspace.data_ptr()
+  args.bias = None if bias is None else bias.data_ptr()
+  if sample_index is not None:
+    if sample_index.dtype != torch.int32 or not sample_index.is_cuda:
+      raise ValueError('sample_index must be an int32 device tensor')
+    args.sample_index = sample_index.data_ptr()
+  for h in range(heads):
+    args.error_floor[h] = float(error_floor[h])
+    args.coef_abs[h] = float(coef_abs[h])
+    args.coef_rel[h] = float(coef_rel[h])
+  args.head_means = head_means.data_ptr()
+  args.grad = None if grad is None else grad.data_ptr()
+  args.predictions = None if preds is None else preds.data_ptr()
+  args.workspace = workspace.data_ptr()
+  args.workspace_bytes = workspace.numel()
+  check(lib.ddd_train_unrolled_loss_grad(ctypes.byref(cfg), ctypes.byref(args),
+                                         current_stream()))
   return head_means, grad, preds
 
 

@@ -34,6 +34,7 @@
 #include "rhs_stream.h"
 #include "ring_args.h"
 #include "train.h"
+#include "train_unrolled.h"
 #include "rhs_weno.h"   // (host side only: weno::supports; the kernels are weno_unit.hip)
 
 namespace {
@@ -1828,6 +1829,47 @@ int train_params(const ddd_config* cfg, int batch, ddd::train::TrainParams* tp, 
   return DDD_OK;
 }
 
+static_assert(ddd::train::kMaxTimeSteps == DDD_MAX_TIME_STEPS, "train_unrolled.h / ddd1d.h");
+static_assert(ddd::train::kMaxUnrolledHeads == DDD_MAX_UNROLLED_HEADS, "train_unrolled.h / ddd1d.h");
+
+// train_params for ddd_train_unrolled_loss_grad (train_unrolled.h): the same checks and
+// messages, then num_time_steps, the wider head part of a slab, the stage states and the
+// integrated heads' cotangents behind the pre-activations, and two more LDS rows under
+// the same 160 KiB check (the staged MFMA kernels are dropped first when they no longer fit).
+int train_unrolled_params(const ddd_config* cfg, int batch, int num_time_steps,
+                          ddd::train::UnrolledParams* up, int* blocks, size_t* ws_bytes,
+                          size_t* lds_bytes) {
+  std::memset(up, 0, sizeof(*up));
+  ddd::train::TrainParams& p = up->t;
+  int rc = train_params(cfg, batch, &p, blocks, ws_bytes, lds_bytes);
+  if (rc) return rc;
+  if (num_time_steps < 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_time_steps = %d (>= 1; ddd_train_loss_grad "
+                "carries the loss without integrated heads)", num_time_steps);
+  if (num_time_steps > DDD_MAX_TIME_STEPS)
+    return fail(DDD_ERR_UNSUPPORTED, "training: num_time_steps = %d > %d", num_time_steps,
+                DDD_MAX_TIME_STEPS);
+  const int T = num_time_steps;
+  up->T = T;
+  up->HT = p.H + T;
+  const size_t z_floats = p.slab_stride - (size_t)p.n_slab;
+  p.n_slab = (int)(((size_t)p.n_weights + 2 * up->HT + 3) & ~(size_t)3);
+  up->st_off = (int)((size_t)p.n_slab + z_floats);
+  up->gi_off = up->st_off + 2 * T * p.N;
+  p.slab_stride = ((size_t)up->gi_off + (size_t)T * p.N + 3) & ~(size_t)3;
+  *ws_bytes = (size_t)*blocks * p.slab_stride * sizeof(float);
+  if (p.mfma && ddd::train::unrolled_lds_floats(p) * sizeof(float) > 160 * 1024) {
+    p.mfma = 0;
+    p.wl_floats = 0;
+    for (int l = 0; l < p.L; ++l) p.wl_off[l] = -1;
+  }
+  *lds_bytes = ddd::train::unrolled_lds_floats(p) * sizeof(float);
+  if (*lds_bytes > 160 * 1024)
+    return fail(DDD_ERR_UNSUPPORTED, "training: %zu bytes of LDS needed (> 160 KiB)",
+                *lds_bytes);
+  return DDD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2904,6 +2946,72 @@ int ddd_train_loss_grad(const ddd_config* cfg, const ddd_train_args* a, void* st
   p.grad = a->grad;
   p.head_means = a->head_means;
   DDD_HIP(ddd::train::launch_loss_grad(p, blocks, lds, static_cast<hipStream_t>(stream)));
+  return DDD_OK;
+}
+
+size_t ddd_train_unrolled_workspace_bytes(const ddd_config* cfg, int batch, int num_time_steps) {
+  ddd::train::UnrolledParams q;
+  int blocks = 0;
+  size_t ws = 0, lds = 0;
+  if (train_unrolled_params(cfg, batch, num_time_steps, &q, &blocks, &ws, &lds)) return 0;
+  return ws;
+}
+
+int ddd_train_unrolled_loss_grad(const ddd_config* cfg, const ddd_train_unrolled_args* a,
+                                 void* stream) {
+  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
+  if (a->struct_size != (int32_t)sizeof(ddd_train_unrolled_args))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_train_unrolled_args.struct_size = %d, library expects %d (ABI mismatch)",
+                a->struct_size, (int)sizeof(ddd_train_unrolled_args));
+  ddd::train::UnrolledParams q;
+  ddd::train::TrainParams& p = q.t;
+  int blocks = 0;
+  size_t ws = 0, lds = 0;
+  int rc = train_unrolled_params(cfg, a->batch, a->num_time_steps, &q, &blocks, &ws, &lds);
+  if (rc) return rc;
+  if (!a->weights || !a->y || !a->labels || !a->baseline || !a->head_means)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "weights, y, labels, baseline and head_means must not be NULL");
+  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
+  if (projected && (!a->nullspace || !a->bias))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "nullspace/bias required for model_target 'coefficients' with "
+                "polynomial_accuracy_order > 0");
+  if (a->num_rows < 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
+  if (a->sample_index == nullptr && a->batch > a->num_rows)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "batch = %d > num_rows = %d without a sample_index", a->batch, a->num_rows);
+  if (!std::isfinite(a->time_step))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
+  if (a->workspace == nullptr || a->workspace_bytes < ws)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "workspace of %zu bytes given, ddd_train_unrolled_workspace_bytes = %zu",
+                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws);
+  for (int h = 0; h < q.HT; ++h) {
+    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
+        !std::isfinite(a->coef_rel[h]))
+      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
+    q.floor[h] = a->error_floor[h];
+    q.coef_abs[h] = a->coef_abs[h];
+    q.coef_rel[h] = a->coef_rel[h];
+  }
+  q.dt = a->time_step;
+  p.weights = a->weights;
+  p.nullspace = projected ? a->nullspace : nullptr;
+  p.bias = projected ? a->bias : nullptr;
+  p.y = a->y;
+  p.sample_index = a->sample_index;
+  p.rows = a->num_rows;
+  p.labels = a->labels;
+  p.baseline = a->baseline;
+  p.predictions = a->predictions;
+  p.ws = static_cast<float*>(a->workspace);
+  p.want_grad = a->grad != nullptr ? 1 : 0;
+  p.grad = a->grad;
+  p.head_means = a->head_means;
+  DDD_HIP(ddd::train::launch_unrolled_loss_grad(q, blocks, lds, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }
 

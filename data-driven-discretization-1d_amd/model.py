@@ -1107,9 +1107,14 @@ def baseline_result(inputs, equation, num_time_steps: int = 0, accuracy_order=No
   accuracy_order=None: the exact equation's derivatives (WENO5 + Godunov flux for
   the Burgers family, spectral derivatives for KdV / KS); flux equations with an
   explicit order are evaluated in their conservative form."""
-  if num_time_steps:
-    raise NotImplementedError('num_time_steps > 0 (integrated_solution) is not supported')
   import torch
+
+  def integrated(x):
+    # model.py:268-272: always the first-order polynomial stencils of the resolved equation
+    if not num_time_steps:
+      return None
+    return baseline_time_evolution(x, num_time_steps, equation).to(torch.float32)
+
   if accuracy_order is None:
     equation = equation.to_exact()
     if equation.EXACT_METHOD is equations_lib.ExactMethod.SPECTRAL:
@@ -1123,7 +1128,7 @@ def baseline_result(inputs, equation, num_time_steps: int = 0, accuracy_order=No
            for order in equation.DERIVATIVE_ORDERS], axis=-1).astype(np.float32),
                               device=x.device)
       time = apply_space_derivatives(space, x, equation)
-      return result_stack(space, time)
+      return result_stack(space, time, integrated(x))
     model = BaselineModel(equation, accuracy_order=None)
   else:
     if type(equation) in equations_lib.FLUX_EQUATION_TYPES.values():
@@ -1134,7 +1139,7 @@ def baseline_result(inputs, equation, num_time_steps: int = 0, accuracy_order=No
     time = model.time_derivative(inputs).to(torch.float32)
   finally:
     model.close()
-  return result_stack(space, time)
+  return result_stack(space, time, integrated(inputs))
 
 
 def apply_noise(inputs, probability: float = 1.0, amplitude: float = 1.0,
@@ -1265,11 +1270,10 @@ def make_dataset(snapshots, hparams, dataset_type: Dataset = Dataset.TRAINING,
 
 def predict_result(inputs, model: LearnedStencilModel):
   """model.py:664-697: [batch, x, channel] = space derivatives and time derivative
-  (zeros for the space derivatives of a time_derivative / flux target)."""
+  (zeros for the space derivatives of a time_derivative / flux target), then, with
+  hparams.num_time_steps > 0, predict_time_evolution."""
   import torch
   hp = model.hparams
-  if hp.num_time_steps:
-    raise NotImplementedError('num_time_steps > 0 (integrated_solution) is not supported')
   x = _lib.as_device(inputs, torch.float32)
   if hp.model_target in ('flux', 'time_derivative'):
     if hp.space_derivatives_weight:
@@ -1281,7 +1285,8 @@ def predict_result(inputs, model: LearnedStencilModel):
   else:
     space = predict_space_derivatives(x, model)
     time = apply_space_derivatives(space, x, model.equation)
-  return result_stack(space, time)
+  integrated = predict_time_evolution(x, model) if hp.num_time_steps else None
+  return result_stack(space, time, integrated)
 
 
 def abs_and_rel_error(predictions, labels, baseline, error_floor=1e-7):

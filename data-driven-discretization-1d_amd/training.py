@@ -1,5 +1,6 @@
 """The reference's training loop (training.py) over the fused HIP loss-and-gradient
-kernel (ddd_train_loss_grad, csrc/train.hip), without TensorFlow.
+kernels (ddd_train_loss_grad, csrc/train.hip; with num_time_steps > 0
+ddd_train_unrolled_loss_grad, csrc/train_unrolled.hip), without TensorFlow.
 
 Reference: training.py:168-189 (set_data_dependent_hparams), 358-417
 (determine_loss_scales), 570-636 (training_loop); model.py:664-810 for the loss.
@@ -40,6 +41,26 @@ def check_supported(hparams):
   if hparams.model_target == 'time_derivative' and hparams.space_derivatives_weight:
     raise ValueError('space derivatives are not predicted by model {}'.format(
         hparams.model_target))
+
+
+def check_supported_through_time(hparams):
+  """check_supported for hparams with num_time_steps > 0 (the integrated_solution loss,
+  ddd_train_unrolled_loss_grad): the same rules, and 1 <= num_time_steps <=
+  DDD_MAX_TIME_STEPS."""
+  steps = hparams.num_time_steps
+  if not steps or steps < 1:
+    raise NotImplementedError('training through time: num_time_steps = {} (>= 1 needed; '
+                              'check_supported covers 0)'.format(steps))
+  if steps > _lib.MAX_TIME_STEPS:
+    raise NotImplementedError('training through time: num_time_steps = {} > {}'.format(
+        steps, _lib.MAX_TIME_STEPS))
+  single = copy.copy(hparams)
+  single.num_time_steps = 0
+  check_supported(single)
+
+
+def _checker(hparams):
+  return check_supported_through_time if hparams.num_time_steps else check_supported
 
 
 def determine_loss_scales(dataset: model_lib.DeviceDataset, hparams):
@@ -101,7 +122,7 @@ class Trainer(object):
     self.torch = torch
     self.model = model
     self.hparams = hparams or model.hparams
-    check_supported(self.hparams)
+    _checker(self.hparams)(self.hparams)
     self.cfg = _train_config(model)
     flat = np.concatenate([np.concatenate([w.ravel(), b.ravel()])
                            for w, b in zip(model.conv_kernels, model.conv_biases)])
@@ -151,6 +172,11 @@ class Trainer(object):
     return per_head, grad, preds
 
   def _call(self, dataset, floor, coef_abs, coef_rel, **kwargs):
+    steps = self.hparams.num_time_steps
+    if steps:   # the integrated heads too: the kernel through time
+      return _lib.train_unrolled_loss_grad(
+          self.cfg, self.weights.detach(), dataset.inputs, dataset.labels, dataset.baseline,
+          floor, coef_abs, coef_rel, steps, self.model.equation.time_step, **kwargs)
     means, grad, preds = _lib.train_loss_grad(
         self.cfg, self.weights.detach(), dataset.inputs, dataset.labels, dataset.baseline,
         floor, coef_abs, coef_rel, **kwargs)
@@ -187,7 +213,7 @@ def training_loop(snapshots: np.ndarray, checkpoint_dir: str, hparams,
   per eval_interval steps: the validation loss and loss per head.  num_steps defaults
   to learning_stops[-1]."""
   hparams = copy.deepcopy(hparams)
-  check_supported(hparams)
+  _checker(hparams)(hparams)
   train_data = set_data_dependent_hparams(hparams, snapshots, seed)
   train_data.repeat = True
   valid_data = model_lib.make_dataset(snapshots, hparams, model_lib.Dataset.VALIDATION,

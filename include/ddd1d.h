@@ -498,6 +498,55 @@ DDD_API size_t ddd_train_workspace_bytes(const ddd_config* cfg, int batch);
 DDD_API int ddd_train_loss_grad(const ddd_config* cfg, const ddd_train_args* args,
                                 void* stream);
 
+/* ---- training through time ------------------------------------------------
+ * Replaces: the same loss with hparams.num_time_steps = T > 0, i.e. with
+ * model.predict_time_evolution (model.py:643-661) appended to predict_result
+ * (model.py:686-696): T more heads, the model's own midpoint-rule trajectory
+ * y(t_1) .. y(t_T) from the input row with step `time_step` (the equation of
+ * motion without forcing), compared with the integrated_solution channels of
+ * the labels.  H' = num_derivatives + 1 + T heads in result_stack order: the
+ * space derivatives, the time derivative, then y(t_1) .. y(t_T).  One launch
+ * runs the 2 T evaluations of the unroll forward and the adjoint of the
+ * midpoint rule backward, per sample, plus the fixed-order slab sum.
+ * Supports exactly the configurations ddd_train_loss_grad supports (same
+ * messages), with 1 <= T <= DDD_MAX_TIME_STEPS. */
+#define DDD_MAX_TIME_STEPS 8
+#define DDD_MAX_UNROLLED_HEADS (DDD_MAX_HEADS + DDD_MAX_TIME_STEPS)
+
+typedef struct ddd_train_unrolled_args {
+  int32_t struct_size;   /* = sizeof(ddd_train_unrolled_args), checked */
+  int32_t batch;         /* samples in the minibatch */
+  int32_t num_rows;      /* S: rows of y / labels / baseline */
+  int32_t num_time_steps; /* T */
+  const float* weights;  /* as ddd_train_args */
+  const float* nullspace; /* as ddd_train_args */
+  const float* bias;     /* as ddd_train_args */
+  const float* y;        /* [S][N] coarse inputs */
+  const int32_t* sample_index; /* as ddd_train_args */
+  const float* labels;   /* [S][N][H'] */
+  const float* baseline; /* [S][N][H'] */
+  float time_step;       /* the equation's time_step */
+  float error_floor[DDD_MAX_UNROLLED_HEADS]; /* HOST values, first H' used */
+  float coef_abs[DDD_MAX_UNROLLED_HEADS];
+  float coef_rel[DDD_MAX_UNROLLED_HEADS];
+  float* head_means;     /* out [2][H'] */
+  float* grad;           /* out, layout of `weights`; NULL = forward and loss only */
+  float* predictions;    /* out [batch][N][H'] or NULL */
+  void* workspace;       /* ddd_train_unrolled_workspace_bytes(cfg, batch, T) bytes */
+  size_t workspace_bytes;
+} ddd_train_unrolled_args;
+
+/* Bytes of the caller-allocated workspace of ddd_train_unrolled_loss_grad
+ * (partial gradient slabs, per-workgroup scratch and stage states); 0 on error. */
+DDD_API size_t ddd_train_unrolled_workspace_bytes(const ddd_config* cfg, int batch,
+                                                  int num_time_steps);
+/* head_means and, with grad non-NULL, the gradient of
+ * sum_h coef_abs[h] head_means[0][h] + coef_rel[h] head_means[1][h] over all H'
+ * heads with respect to every conv kernel and bias.  Deterministic, sample_index,
+ * grad = NULL, predictions = NULL and error_max clipping as ddd_train_loss_grad. */
+DDD_API int ddd_train_unrolled_loss_grad(const ddd_config* cfg,
+                                         const ddd_train_unrolled_args* args, void* stream);
+
 /* ---- differentiable evaluation --------------------------------------------
  * Replaces: tf.gradients through model.predict_result (model.py:664-697), the
  * building block of the reference's differentiable time integration
