@@ -419,6 +419,65 @@ def circulant_apply(kernel, inputs):
   return out
 
 
+def _train_call(entry, workspace_bytes, args, steps, cfg, weights, y, labels, baseline,
+                error_floor, coef_abs, coef_rel, nullspace, bias, sample_index, batch,
+                want_grad, want_predictions, workspace):
+  """The body of train_loss_grad (steps None) / train_unrolled_loss_grad: shape checks,
+  workspace, outputs and `args` (a DDDTrainArgs or DDDTrainUnrolledArgs with its own
+  fields already set) filled, then `entry`.  workspace_bytes(batch) is the entry point's
+  workspace size."""
+  torch = require_gpu()
+  extra_heads = 0 if steps is None else steps
+  heads_text = 'num_derivatives + 1' + ('' if steps is None else ' + num_time_steps')
+  shape_text = '[S, N, H]' if steps is None else "[S, N, H']"
+  if batch is None:
+    batch = int(sample_index.shape[0]) if sample_index is not None else int(y.shape[0])
+  heads = int(labels.shape[-1])
+  if heads != cfg.num_derivatives + 1 + extra_heads:
+    raise ValueError('labels must have {} = {} channels, got {}'.format(
+        heads_text, cfg.num_derivatives + 1 + extra_heads, heads))
+  if (y.dim() != 2 or tuple(labels.shape) != tuple(y.shape) + (heads,) or
+      tuple(baseline.shape) != tuple(labels.shape) or y.shape[1] != cfg.num_points):
+    raise ValueError('expected y [S, N], labels / baseline {}'.format(shape_text))
+  if sample_index is not None and (sample_index.dim() != 1 or
+                                   int(sample_index.shape[0]) != batch):
+    raise ValueError('sample_index must have `batch` entries')
+  ws_bytes = workspace_bytes(int(batch))
+  if ws_bytes == 0:
+    check(-1)
+  if workspace is None or workspace.numel() < ws_bytes:
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
+  head_means = torch.empty((2, heads), dtype=torch.float32, device=y.device)
+  grad = torch.empty_like(weights) if want_grad else None
+  preds = (torch.empty((batch, y.shape[1], heads), dtype=torch.float32, device=y.device)
+           if want_predictions else None)
+  args.struct_size = ctypes.sizeof(args)
+  args.batch = int(batch)
+  args.num_rows = int(y.shape[0])
+  for name, tensor in (('weights', weights), ('y', y), ('labels', labels),
+                       ('baseline', baseline)):
+    if tensor.dtype != torch.float32 or not tensor.is_contiguous() or not tensor.is_cuda:
+      raise ValueError('{} must be a contiguous float32 device tensor'.format(name))
+    setattr(args, name, tensor.data_ptr())
+  args.nullspace = None if nullspace is None else nullspace.data_ptr()
+  args.bias = None if bias is None else bias.data_ptr()
+  if sample_index is not None:
+    if sample_index.dtype != torch.int32 or not sample_index.is_cuda:
+      raise ValueError('sample_index must be an int32 device tensor')
+    args.sample_index = sample_index.data_ptr()
+  for h in range(heads):
+    args.error_floor[h] = float(error_floor[h])
+    args.coef_abs[h] = float(coef_abs[h])
+    args.coef_rel[h] = float(coef_rel[h])
+  args.head_means = head_means.data_ptr()
+  args.grad = None if grad is None else grad.data_ptr()
+  args.predictions = None if preds is None else preds.data_ptr()
+  args.workspace = workspace.data_ptr()
+  args.workspace_bytes = workspace.numel()
+  check(entry(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
+  return head_means, grad, preds
+
+
 def train_loss_grad(cfg, weights, y, labels, baseline, error_floor, coef_abs, coef_rel,
                     nullspace=None, bias=None, sample_index=None, batch=None,
                     want_grad=True, want_predictions=False, workspace=None):
@@ -430,54 +489,10 @@ def train_loss_grad(cfg, weights, y, labels, baseline, error_floor, coef_abs, co
   uint8 device tensor of at least ddd_train_workspace_bytes bytes, reused across
   calls when given."""
   lib = load_library()
-  torch = require_gpu()
-  if batch is None:
-    batch = int(sample_index.shape[0]) if sample_index is not None else int(y.shape[0])
-  heads = int(labels.shape[-1])
-  if heads != cfg.num_derivatives + 1:
-    raise ValueError('labels must have num_derivatives + 1 = {} channels, got {}'.format(
-        cfg.num_derivatives + 1, heads))
-  if (y.dim() != 2 or tuple(labels.shape) != tuple(y.shape) + (heads,) or
-      tuple(baseline.shape) != tuple(labels.shape) or y.shape[1] != cfg.num_points):
-    raise ValueError('expected y [S, N], labels / baseline [S, N, H]')
-  if sample_index is not None and (sample_index.dim() != 1 or
-                                   int(sample_index.shape[0]) != batch):
-    raise ValueError('sample_index must have `batch` entries')
-  ws_bytes = lib.ddd_train_workspace_bytes(ctypes.byref(cfg), int(batch))
-  if ws_bytes == 0:
-    check(-1)
-  if workspace is None or workspace.numel() < ws_bytes:
-    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
-  head_means = torch.empty((2, heads), dtype=torch.float32, device=y.device)
-  grad = torch.empty_like(weights) if want_grad else None
-  preds = (torch.empty((batch, y.shape[1], heads), dtype=torch.float32, device=y.device)
-           if want_predictions else None)
-  args = DDDTrainArgs()
-  args.struct_size = ctypes.sizeof(DDDTrainArgs)
-  args.batch = int(batch)
-  args.num_rows = int(y.shape[0])
-  for name, tensor in (('weights', weights), ('y', y), ('labels', labels),
-                       ('baseline', baseline)):
-    if tensor.dtype != torch.float32 or not tensor.is_contiguous() or not tensor.is_cuda:
-      raise ValueError('{} must be a contiguous float32 device tensor'.format(name))
-    setattr(args, name, tensor.data_ptr())
-  args.nullspace = None if nullspace is None else nullspace.data_ptr()
-  args.bias = None if bias is None else bias.data_ptr()
-  if sample_index is not None:
-    if sample_index.dtype != torch.int32 or not sample_index.is_cuda:
-      raise ValueError('sample_index must be an int32 device tensor')
-    args.sample_index = sample_index.data_ptr()
-  for h in range(heads):
-    args.error_floor[h] = float(error_floor[h])
-    args.coef_abs[h] = float(coef_abs[h])
-    args.coef_rel[h] = float(coef_rel[h])
-  args.head_means = head_means.data_ptr()
-  args.grad = None if grad is None else grad.data_ptr()
-  args.predictions = None if preds is None else preds.data_ptr()
-  args.workspace = workspace.data_ptr()
-  args.workspace_bytes = workspace.numel()
-  check(lib.ddd_train_loss_grad(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
-  return head_means, grad, preds
+  return _train_call(
+      lib.ddd_train_loss_grad, lambda b: lib.ddd_train_workspace_bytes(ctypes.byref(cfg), b),
+      DDDTrainArgs(), None, cfg, weights, y, labels, baseline, error_floor, coef_abs, coef_rel,
+      nullspace, bias, sample_index, batch, want_grad, want_predictions, workspace)
 
 
 def train_unrolled_loss_grad(cfg, weights, y, labels, baseline, error_floor, coef_abs,
@@ -488,58 +503,15 @@ def train_unrolled_loss_grad(cfg, weights, y, labels, baseline, error_floor, coe
   None) with H' = num_derivatives + 1 + num_time_steps heads; the other arguments as
   train_loss_grad, labels / baseline [S, N, H'], error_floor / coef_* H' host floats."""
   lib = load_library()
-  torch = require_gpu()
   steps = int(num_time_steps)
-  if batch is None:
-    batch = int(sample_index.shape[0]) if sample_index is not None else int(y.shape[0])
-  heads = int(labels.shape[-1])
-  if heads != cfg.num_derivatives + 1 + steps:
-    raise ValueError('labels must have num_derivatives + 1 + num_time_steps = {} channels, '
-                     'got {}'.format(cfg.num_derivatives + 1 + steps, heads))
-  if (y.dim() != 2 or tuple(labels.shape) != tuple(y.shape) + (heads,) or
-      tuple(baseline.shape) != tuple(labels.shape) or y.shape[1] != cfg.num_points):
-    raise ValueError("expected y [S, N], labels / baseline [S, N, H']")
-  if sample_index is not None and (sample_index.dim() != 1 or
-                                   int(sample_index.shape[0]) != batch):
-    raise ValueError('sample_index must have `batch` entries')
-  ws_bytes = lib.ddd_train_unrolled_workspace_bytes(ctypes.byref(cfg), int(batch), steps)
-  if ws_bytes == 0:
-    check(-1)
-  if workspace is None or workspace.numel() < ws_bytes:
-    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
-  head_means = torch.empty((2, heads), dtype=torch.float32, device=y.device)
-  grad = torch.empty_like(weights) if want_grad else None
-  preds = (torch.empty((batch, y.shape[1], heads), dtype=torch.float32, device=y.device)
-           if want_predictions else None)
   args = DDDTrainUnrolledArgs()
-  args.struct_size = ctypes.sizeof(DDDTrainUnrolledArgs)
-  args.batch = int(batch)
-  args.num_rows = int(y.shape[0])
   args.num_time_steps = steps
   args.time_step = float(time_step)
-  for name, tensor in (('weights', weights), ('y', y), ('labels', labels),
-                       ('baseline', baseline)):
-    if tensor.dtype != torch.float32 or not tensor.is_contiguous() or not tensor.is_cuda:
-      raise ValueError('{} must be a contiguous float32 device tensor'.format(name))
-    setattr(args, name, tensor.data_ptr())
-  args.nullspace = None if nullspace is None else nullspace.data_ptr()
-  args.bias = None if bias is None else bias.data_ptr()
-  if sample_index is not None:
-    if sample_index.dtype != torch.int32 or not sample_index.is_cuda:
-      raise ValueError('sample_index must be an int32 device tensor')
-    args.sample_index = sample_index.data_ptr()
-  for h in range(heads):
-    args.error_floor[h] = float(error_floor[h])
-    args.coef_abs[h] = float(coef_abs[h])
-    args.coef_rel[h] = float(coef_rel[h])
-  args.head_means = head_means.data_ptr()
-  args.grad = None if grad is None else grad.data_ptr()
-  args.predictions = None if preds is None else preds.data_ptr()
-  args.workspace = workspace.data_ptr()
-  args.workspace_bytes = workspace.numel()
-  check(lib.ddd_train_unrolled_loss_grad(ctypes.byref(cfg), ctypes.byref(args),
-                                         current_stream()))
-  return head_means, grad, preds
+  return _train_call(
+      lib.ddd_train_unrolled_loss_grad,
+      lambda b: lib.ddd_train_unrolled_workspace_bytes(ctypes.byref(cfg), b, steps),
+      args, steps, cfg, weights, y, labels, baseline, error_floor, coef_abs, coef_rel,
+      nullspace, bias, sample_index, batch, want_grad, want_predictions, workspace)
 
 
 def _check_f32_device(name, tensor, shape):

@@ -1870,6 +1870,56 @@ int train_unrolled_params(const ddd_config* cfg, int batch, int num_time_steps,
   return DDD_OK;
 }
 
+// What ddd_train_loss_grad and ddd_train_unrolled_loss_grad check and copy alike, for
+// Args = ddd_train_args / ddd_train_unrolled_args (equally named fields): the argument
+// pointers into p and the `heads` per-head loss constants into floor / coef_abs / coef_rel.
+// ws_bytes_fn names the entry point's workspace function in the message.
+template <typename Args>
+int train_args(const Args* a, ddd::train::TrainParams& p, size_t ws, const char* ws_bytes_fn,
+               int heads, float* floor, float* coef_abs, float* coef_rel) {
+  if (!a->weights || !a->y || !a->labels || !a->baseline || !a->head_means)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "weights, y, labels, baseline and head_means must not be NULL");
+  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
+  if (projected && (!a->nullspace || !a->bias))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "nullspace/bias required for model_target 'coefficients' with "
+                "polynomial_accuracy_order > 0");
+  if (a->num_rows < 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
+  if (a->sample_index == nullptr && a->batch > a->num_rows)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "batch = %d > num_rows = %d without a sample_index", a->batch, a->num_rows);
+  if constexpr (std::is_same<Args, ddd_train_unrolled_args>::value)
+    if (!std::isfinite(a->time_step))
+      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
+  if (a->workspace == nullptr || a->workspace_bytes < ws)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "workspace of %zu bytes given, %s = %zu",
+                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws_bytes_fn, ws);
+  for (int h = 0; h < heads; ++h) {
+    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
+        !std::isfinite(a->coef_rel[h]))
+      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
+    floor[h] = a->error_floor[h];
+    coef_abs[h] = a->coef_abs[h];
+    coef_rel[h] = a->coef_rel[h];
+  }
+  p.weights = a->weights;
+  p.nullspace = projected ? a->nullspace : nullptr;
+  p.bias = projected ? a->bias : nullptr;
+  p.y = a->y;
+  p.sample_index = a->sample_index;
+  p.rows = a->num_rows;
+  p.labels = a->labels;
+  p.baseline = a->baseline;
+  p.predictions = a->predictions;
+  p.ws = static_cast<float*>(a->workspace);
+  p.want_grad = a->grad != nullptr ? 1 : 0;
+  p.grad = a->grad;
+  p.head_means = a->head_means;
+  return DDD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2907,44 +2957,8 @@ int ddd_train_loss_grad(const ddd_config* cfg, const ddd_train_args* a, void* st
   size_t ws = 0, lds = 0;
   int rc = train_params(cfg, a->batch, &p, &blocks, &ws, &lds);
   if (rc) return rc;
-  if (!a->weights || !a->y || !a->labels || !a->baseline || !a->head_means)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "weights, y, labels, baseline and head_means must not be NULL");
-  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
-  if (projected && (!a->nullspace || !a->bias))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "nullspace/bias required for model_target 'coefficients' with "
-                "polynomial_accuracy_order > 0");
-  if (a->num_rows < 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
-  if (a->sample_index == nullptr && a->batch > a->num_rows)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "batch = %d > num_rows = %d without a sample_index", a->batch, a->num_rows);
-  if (a->workspace == nullptr || a->workspace_bytes < ws)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "workspace of %zu bytes given, ddd_train_workspace_bytes = %zu",
-                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws);
-  for (int h = 0; h < p.H; ++h) {
-    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
-        !std::isfinite(a->coef_rel[h]))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
-    p.floor[h] = a->error_floor[h];
-    p.coef_abs[h] = a->coef_abs[h];
-    p.coef_rel[h] = a->coef_rel[h];
-  }
-  p.weights = a->weights;
-  p.nullspace = projected ? a->nullspace : nullptr;
-  p.bias = projected ? a->bias : nullptr;
-  p.y = a->y;
-  p.sample_index = a->sample_index;
-  p.rows = a->num_rows;
-  p.labels = a->labels;
-  p.baseline = a->baseline;
-  p.predictions = a->predictions;
-  p.ws = static_cast<float*>(a->workspace);
-  p.want_grad = a->grad != nullptr ? 1 : 0;
-  p.grad = a->grad;
-  p.head_means = a->head_means;
+  rc = train_args(a, p, ws, "ddd_train_workspace_bytes", p.H, p.floor, p.coef_abs, p.coef_rel);
+  if (rc) return rc;
   DDD_HIP(ddd::train::launch_loss_grad(p, blocks, lds, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }
@@ -2970,47 +2984,10 @@ int ddd_train_unrolled_loss_grad(const ddd_config* cfg, const ddd_train_unrolled
   size_t ws = 0, lds = 0;
   int rc = train_unrolled_params(cfg, a->batch, a->num_time_steps, &q, &blocks, &ws, &lds);
   if (rc) return rc;
-  if (!a->weights || !a->y || !a->labels || !a->baseline || !a->head_means)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "weights, y, labels, baseline and head_means must not be NULL");
-  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
-  if (projected && (!a->nullspace || !a->bias))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "nullspace/bias required for model_target 'coefficients' with "
-                "polynomial_accuracy_order > 0");
-  if (a->num_rows < 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
-  if (a->sample_index == nullptr && a->batch > a->num_rows)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "batch = %d > num_rows = %d without a sample_index", a->batch, a->num_rows);
-  if (!std::isfinite(a->time_step))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
-  if (a->workspace == nullptr || a->workspace_bytes < ws)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "workspace of %zu bytes given, ddd_train_unrolled_workspace_bytes = %zu",
-                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws);
-  for (int h = 0; h < q.HT; ++h) {
-    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
-        !std::isfinite(a->coef_rel[h]))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
-    q.floor[h] = a->error_floor[h];
-    q.coef_abs[h] = a->coef_abs[h];
-    q.coef_rel[h] = a->coef_rel[h];
-  }
+  rc = train_args(a, p, ws, "ddd_train_unrolled_workspace_bytes", q.HT, q.floor, q.coef_abs,
+                  q.coef_rel);
+  if (rc) return rc;
   q.dt = a->time_step;
-  p.weights = a->weights;
-  p.nullspace = projected ? a->nullspace : nullptr;
-  p.bias = projected ? a->bias : nullptr;
-  p.y = a->y;
-  p.sample_index = a->sample_index;
-  p.rows = a->num_rows;
-  p.labels = a->labels;
-  p.baseline = a->baseline;
-  p.predictions = a->predictions;
-  p.ws = static_cast<float*>(a->workspace);
-  p.want_grad = a->grad != nullptr ? 1 : 0;
-  p.grad = a->grad;
-  p.head_means = a->head_means;
   DDD_HIP(ddd::train::launch_unrolled_loss_grad(q, blocks, lds, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }

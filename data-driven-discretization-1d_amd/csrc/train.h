@@ -1,13 +1,15 @@
 // Training: the loss of model.py:704-810 and its gradient with respect to the conv
 // weights, for one minibatch, fused into one kernel (ddd_train_loss_grad, include/ddd1d.h).
-// This header carries the kernel parameters; the kernels are in train.hip.
+// This header carries the kernel parameters and the host-side launchers; the kernel is in
+// train.hip, the device code it shares with vjp.hip and train_unrolled.hip in
+// train_device.h.
 //
 // One workgroup walks over samples s = blockIdx.x, blockIdx.x + gridDim.x, ... and, per
 // sample, recomputes the forward pass (input scaling, the periodic conv tower, the
 // projection, the stencils and the equation of motion), forms the elementwise loss
 // cotangent and runs the backward pass down to the conv weights.  The weight gradient of
 // every sample the workgroup owns is added, in sample order, into the workgroup's own
-// partial slab of the caller's workspace; reduce_kernel then sums the slabs in workgroup
+// partial slab of the caller's workspace; slab_sum_kernel then sums the slabs in workgroup
 // order.  No atomics anywhere: equal inputs give equal bits.
 //
 // The pre-activations of the hidden layers go to the slab's scratch part (global memory,
@@ -59,24 +61,34 @@ struct TrainParams {
   float* head_means;       // [2][H]
 };
 
+// The LDS plan of a workgroup (train_device.h: Rows): rows of [N] (the state, the
+// time-derivative cotangent, the flux), of [N][H] (predictions, their cotangent, the two
+// error-term rows) and of [N][cmax] (two activation buffers)
+constexpr int kLdsRowsN = 3, kLdsRowsNH = 4, kLdsRowsNC = 2;
 __host__ __device__ inline size_t lds_floats(const TrainParams& p) {
-  // u, the flux / time-derivative cotangent, a spare row; predictions, cotangents and
-  // the two error terms per (point, head); two activation buffers
-  return 3 * (size_t)p.N + 4 * (size_t)p.N * p.H + 2 * (size_t)p.N * p.cmax;
+  return kLdsRowsN * (size_t)p.N + kLdsRowsNH * (size_t)p.N * p.H +
+         kLdsRowsNC * (size_t)p.N * p.cmax;
 }
 // ... plus the staged 32 x 32 kernels of the MFMA layers
 __host__ __device__ inline size_t lds_total_floats(const TrainParams& p) {
   return lds_floats(p) + (size_t)p.wl_floats;
 }
 
-// loss_grad_kernel on `blocks` workgroups, then reduce_kernel (train.hip)
+// `kernel` (one by-value parameter struct at `params`, p its TrainParams) on `blocks`
+// workgroups with lds_bytes of dynamic LDS, then, when first < total, slab_sum_kernel
+// over the slab indices [first, total): grad below p.n_weights, head_means behind it
+// (train.hip).  The one launcher of the three kernels below.
+hipError_t launch_then_sum(const void* kernel, const void* params, const TrainParams& p,
+                           int blocks, size_t lds_bytes, hipStream_t stream, int first,
+                           int total);
+
+// loss_grad_kernel on `blocks` workgroups, then the slab sum (train.hip)
 hipError_t launch_loss_grad(const TrainParams& p, int blocks, size_t lds_bytes, hipStream_t stream);
 
 // The vector-Jacobian product of one model evaluation (ddd_result_vjp, vjp.hip): the
-// forward pass of loss_grad_kernel, then, with a cotangent, its backward pass from that
+// forward pass of training, then, with a cotangent, the same backward pass from that
 // cotangent instead of the loss's, down to the weights and to the state.  Same
-// configurations, workspace and LDS plan as training (the error-term rows hold the
-// space-derivative cotangents and the state gradient).
+// configurations, workspace and LDS plan as training.
 struct VjpParams {
   TrainParams t;           // configuration, weights, y (rows = batch, no sample_index),
                            // predictions, ws; want_grad / grad = the weight gradient
@@ -84,7 +96,7 @@ struct VjpParams {
   float* grad_y;           // [batch][N] or null
 };
 
-// vjp_kernel on `blocks` workgroups, then (want_grad) the fixed-order slab sum (vjp.hip)
+// vjp_kernel on `blocks` workgroups, then (want_grad) the slab sum (vjp.hip)
 hipError_t launch_vjp(const VjpParams& q, int blocks, size_t lds_bytes, hipStream_t stream);
 
 }  // namespace train

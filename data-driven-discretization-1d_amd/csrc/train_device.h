@@ -1,12 +1,15 @@
-// Device code shared by the training kernel (train.hip: loss_grad_kernel) and the
-// vector-Jacobian product kernel (vjp.hip: vjp_kernel): activation and equation
-// derivatives and the conv layers on the VALU and on v_mfma_f32_32x32x2_f32.  Below them,
-// the forward pass of one sample and the tower's backward pass as vjp_kernel runs them;
-// loss_grad_kernel keeps its own copy of both inline, instruction for instruction the
-// code its numbers were measured with (passing it through these functions changes its
-// register allocation).
+// Device code shared by the three kernels that differentiate one learned-stencil model
+// evaluation: loss_grad_kernel (train.hip), vjp_kernel (vjp.hip) and
+// unrolled_loss_grad_kernel (train_unrolled.hip).  Activation and equation derivatives, the
+// conv layers on the VALU and on v_mfma_f32_32x32x2_f32, the loss terms of one (point,
+// head), the LDS plan of a workgroup and its prologue, the forward pass of one sample
+// (forward_sample) and its backward pass from a cotangent of the predictions down to the
+// weights and the state (evaluation_vjp, over tower_backward).  Each exists once, here;
+// the kernels differ in where the cotangent comes from and where the state gradient goes.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cstddef>
 
 #include "train.h"
 
@@ -156,6 +159,78 @@ __device__ inline void conv_weight_grad_mfma(const TrainParams& p, const float* 
   }
 }
 
+struct HeadTerms { float abs_error, rel_error, cotangent; };
+
+// abs_and_rel_error and the cotangent of the weighted loss at one (point, head)
+__device__ __forceinline__ HeadTerms head_terms(float pv, float lv, float bv, float floor,
+                                                float coef_abs, float coef_rel,
+                                                float inv_count) {
+  const float diff = lv - pv, base = lv - bv;
+  const float me = diff * diff;
+  const float den = base * base + floor;
+  HeadTerms t;
+  t.abs_error = me;
+  t.rel_error = me / den;
+  t.cotangent = ((2.0f * (pv - lv)) * (coef_abs + coef_rel / den)) * inv_count;
+  return t;
+}
+
+// The LDS rows of one workgroup.  The two [N][H] rows behind gp hold the error terms of
+// the loss until their per-head sums are taken, and the space-derivative cotangents and
+// the state gradient inside evaluation_vjp.
+struct Rows {
+  float* u;      // [N] the state of the current evaluation
+  float* gdy;    // [N] cotangent of the time derivative
+  float* gfl;    // [N] flux (forward) / cotangent of the flux (backward)
+  float* pred;   // [N][H] one evaluation's predictions
+  float* gp;     // [N][H] cotangent of the predictions
+  float* gsd;    // [N][H] cotangents of the space derivatives / abs. error terms
+  float* gu;     // [N][H] state gradient (a) + (b) (first N) / rel. error terms
+  float* buf0;   // [N][cmax]
+  float* buf1;   // [N][cmax]
+  float* wl;     // staged 32 x 32 kernels (p.mfma)
+  float* lam;    // [N] adjoint of the state (through time only)
+  float* gmid;   // [N] state gradient of the midpoint evaluation (through time only)
+};
+
+// Rows over smem, in the order of the struct.  lds_floats (train.h) counts the rows
+// before wl and unrolled_lds_floats (train_unrolled.h) the two behind it: a row added to
+// the struct without its size fails to compile here.
+__device__ __forceinline__ Rows carve_rows(const TrainParams& p, float* smem, bool through_time) {
+  static_assert(offsetof(Rows, wl) / sizeof(float*) == kLdsRowsN + kLdsRowsNH + kLdsRowsNC &&
+                    sizeof(Rows) / sizeof(float*) == kLdsRowsN + kLdsRowsNH + kLdsRowsNC + 1 + 2,
+                "Rows and lds_floats / unrolled_lds_floats disagree");
+  const int n = p.N, H = p.H;
+  Rows r;
+  r.u = smem;
+  r.gdy = r.u + n;
+  r.gfl = r.gdy + n;
+  r.pred = r.gfl + n;
+  r.gp = r.pred + (size_t)n * H;
+  r.gsd = r.gp + (size_t)n * H;
+  r.gu = r.gsd + (size_t)n * H;
+  r.buf0 = r.gu + (size_t)n * H;
+  r.buf1 = r.buf0 + (size_t)n * p.cmax;
+  r.wl = r.buf1 + (size_t)n * p.cmax;
+  r.lam = through_time ? r.wl + p.wl_floats : nullptr;
+  r.gmid = through_time ? r.lam + n : nullptr;
+  return r;
+}
+
+// A workgroup's prologue: the first n_zero floats of its slab cleared (the sums it adds
+// into), the 32 x 32 kernels of the MFMA layers copied into wl.  Block-wide.
+__device__ __forceinline__ void stage_workgroup(const TrainParams& p, float* slab, int n_zero,
+                                                float* wl) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n_zero; i += kThreads) slab[i] = 0.0f;
+  for (int l = 0; l < p.L; ++l) {
+    if (p.wl_off[l] < 0) continue;
+    const float* src = p.weights + p.w_off[l];
+    for (int i = tid; i < p.K * 32 * 32; i += kThreads) wl[p.wl_off[l] + i] = src[i];
+  }
+  __syncthreads();
+}
+
 // The forward pass of one sample whose state is staged in u (and u / stddev in *cur):
 // the tower (model.py:420-513 / 551-615) ping-ponging between *cur and *nxt, the
 // hidden layers' pre-activations to zs, then the stencils and the equation of motion
@@ -297,6 +372,112 @@ __device__ __forceinline__ void tower_backward(const TrainParams& p, const float
     __syncthreads();
     float* t = gz; gz = act_in; act_in = t;
   }
+}
+
+// The vector-Jacobian product of the evaluation whose forward pass has just run, with the
+// cotangent of its predictions in r.gp.  Contract with forward_sample: r.u and r.pred are
+// that evaluation's, zs holds its pre-activations and cur its net output [N][C_out], which
+// term (b) reads before tower_backward overwrites it; nxt is free.  From r.gp back through
+// the equation of motion, the flux difference, the stencils and the projection to the net
+// output, then the tower: the weight gradient is added into slab when want_w, and with
+// grad_y non-null (LDS or global, [N]) the state gradient
+//   grad_y[x] = (a) gfl[x] d r / d y (the explicit state terms of the equation)
+//             + (b) sum_d sum_g gs[x - g + gl, d] coef[x - g + gl, d, g] (transposed
+//                   stencils, gathered: coefficients target only)
+//             + (c) layer 0's transposed convolution / stddev (the tower's input)
+// is stored there, gs[x, d] being the cotangent of space derivative d at x.  r.gdy, r.gfl,
+// r.gsd and r.gu are overwritten, the last two behind two barriers.  kStateGrad false
+// (training: grad_y is null in every call) leaves gs and the state gradient unformed.
+// Block-wide.
+template <bool kStateGrad>
+__device__ __forceinline__ void evaluation_vjp(const TrainParams& p, const Rows& r,
+                                               const float* zs, float* cur, float* nxt,
+                                               float* slab, bool want_w, float* grad_y) {
+  const int tid = threadIdx.x, n = p.N, H = p.H, D = p.D;
+  const bool stencils = p.target == TARGET_COEFFICIENTS;
+  const bool direct_time = p.target == TARGET_TIME_DERIVATIVE;
+  const bool flux_diff = !direct_time && p.conservative;
+  const int gl = p.G / 2;
+  const float* u = r.u;
+  // ---- backward through the equation of motion and the flux difference
+  for (int x = tid; x < n; x += kThreads) r.gdy[x] = r.gp[(size_t)x * H + D];
+  __syncthreads();
+  for (int x = tid; x < n; x += kThreads)
+    r.gfl[x] = flux_diff ? p.inv_dx * (r.gdy[x] - r.gdy[x == 0 ? n - 1 : x - 1]) : r.gdy[x];
+  __syncthreads();
+  // ---- ... the stencils and the projection: d / d net output, into nxt; gs and the
+  // state gradient's term (a)
+  float* gz = nxt;
+  for (int x = tid; x < n; x += kThreads) {
+    if (direct_time) {
+      gz[x] = r.gfl[x];
+      if (kStateGrad) r.gu[x] = 0.0f;
+      continue;
+    }
+    float dv[kMaxDerivs] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int d = 0; d < D; ++d) dv[d] = r.pred[(size_t)x * H + d];
+    if (kStateGrad) r.gu[x] = r.gfl[x] * rhs_state_partial(p.equation, dv);
+    for (int d = 0; d < D; ++d) {
+      const float gs = r.gp[(size_t)x * H + d] +
+                       r.gfl[x] * rhs_partial(p.equation, d, u[x], dv, p.eta);
+      if (kStateGrad) r.gsd[(size_t)x * H + d] = gs;
+      if (p.target == TARGET_SPACE_DERIVATIVES) {
+        gz[(size_t)x * p.C_out + d] = gs;
+      } else if (p.pao == 0) {
+        float mean = 0.0f;
+        if (p.unbiased) {
+          for (int g = 0; g < p.G; ++g) mean += gs * u[wrap(x + g - gl, n)];
+          mean = mean / (float)p.G;
+        }
+        for (int g = 0; g < p.G; ++g)
+          gz[(size_t)x * p.C_out + d * p.G + g] = gs * u[wrap(x + g - gl, n)] - mean;
+      } else {
+        const float* __restrict__ ns = p.nullspace + p.ns_off[d];
+        for (int j = 0; j < p.in_size[d]; ++j) {
+          float acc = 0.0f;
+          for (int g = 0; g < p.G; ++g)
+            acc = fmaf(gs * u[wrap(x + g - gl, n)], ns[j * p.G + g], acc);
+          gz[(size_t)x * p.C_out + p.in_start[d] + j] = acc;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (kStateGrad && grad_y != nullptr && stencils) {
+    // term (b): point x enters the stencil of x - g + gl as tap g; the coefficients are
+    // re-formed from the net output (cur, still live) exactly as forward_sample forms them
+    const float* net = cur;
+    for (int x = tid; x < n; x += kThreads) {
+      float acc = 0.0f;
+      for (int d = 0; d < D; ++d) {
+        for (int g = 0; g < p.G; ++g) {
+          const int xs = wrap(x - g + gl, n);
+          float coeff;
+          if (p.pao == 0) {
+            float mean = 0.0f;
+            if (p.unbiased) {
+              for (int h = 0; h < p.G; ++h) mean += net[(size_t)xs * p.C_out + d * p.G + h];
+              mean = mean / (float)p.G;
+            }
+            coeff = net[(size_t)xs * p.C_out + d * p.G + g] - mean;
+          } else {
+            const float* __restrict__ ns = p.nullspace + p.ns_off[d];
+            const float* __restrict__ nv = net + (size_t)xs * p.C_out + p.in_start[d];
+            float proj = 0.0f;
+            for (int j = 0; j < p.in_size[d]; ++j) proj = fmaf(nv[j], ns[j * p.G + g], proj);
+            coeff = p.bias[d * p.G + g] + proj;
+          }
+          acc = fmaf(r.gsd[(size_t)xs * H + d], coeff, acc);
+        }
+      }
+      r.gu[x] += acc;
+    }
+    __syncthreads();
+  }
+  // ---- the tower, top down (the net output is no longer needed); term (c) and the
+  // state gradient's store at layer 0
+  tower_backward(p, r.wl, zs, u, gz, cur, slab, want_w, r.gu, kStateGrad ? grad_y : nullptr);
+  __syncthreads();
 }
 
 }  // namespace train

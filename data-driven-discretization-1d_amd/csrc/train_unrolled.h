@@ -1,8 +1,8 @@
 // Training through time: the loss of model.py:704-810 over the D + 1 heads of one
 // evaluation AND the T heads of the model's own midpoint trajectory (predict_time_evolution,
 // model.py:643-661), and its gradient with respect to the conv weights, for one minibatch
-// in one kernel (ddd_train_unrolled_loss_grad, include/ddd1d.h).  The kernels are in
-// train_unrolled.hip.
+// in one kernel (ddd_train_unrolled_loss_grad, include/ddd1d.h).  The kernel is in
+// train_unrolled.hip; each evaluation's forward and backward pass is train_device.h's.
 //
 // Per sample a workgroup runs the 2 T evaluations of the unroll forward, keeping the 2 T
 // stage states y_0, y_mid_0, y_1, ... in its scratch slab (global memory, L2-resident),
@@ -37,13 +37,13 @@ struct UnrolledParams {
   float floor[kMaxUnrolledHeads], coef_abs[kMaxUnrolledHeads], coef_rel[kMaxUnrolledHeads];
 };
 
-// the LDS plan of training plus two rows: the adjoint of the state and the state
-// gradient of the midpoint evaluation
+// the LDS plan of training plus two rows behind the staged kernels (Rows::lam, gmid):
+// the adjoint of the state and the state gradient of the midpoint evaluation
 __host__ __device__ inline size_t unrolled_lds_floats(const TrainParams& p) {
   return lds_total_floats(p) + 2 * (size_t)p.N;
 }
 
-// unrolled_loss_grad_kernel on `blocks` workgroups, then the fixed-order slab sum
+// unrolled_loss_grad_kernel on `blocks` workgroups, then the slab sum
 hipError_t launch_unrolled_loss_grad(const UnrolledParams& q, int blocks, size_t lds_bytes,
                                      hipStream_t stream);
 

@@ -10,10 +10,8 @@
 //               (at s = 0 the cotangents of the D + 1 heads ride in the same product),
 //               lam = lam + g_mid + g_s + the loss cotangent of head y(t_s) (s >= 1)
 //             every product adds its weight gradient to the workgroup's slab.
-// The forward pass and the tower's backward pass are train_device.h's; the backward pass
-// through the equation of motion and the stencils, and the state gradient's terms (a)
-// and (b), are those of vjp_kernel (vjp.hip), restated here so that vjp_kernel's code
-// stays what it was measured as.
+// The forward pass of an evaluation, its vector-Jacobian product, the loss terms and the
+// LDS plan are train_device.h's (forward_sample, evaluation_vjp, head_terms, Rows).
 #include <hip/hip_runtime.h>
 
 #include "train_device.h"
@@ -22,155 +20,12 @@
 namespace ddd {
 namespace train {
 
-namespace {
-
-struct HeadTerms { float abs_error, rel_error, cotangent; };
-
-// abs_and_rel_error and the cotangent of the weighted loss at one (point, head)
-__device__ __forceinline__ HeadTerms head_terms(float pv, float lv, float bv, float floor,
-                                                float coef_abs, float coef_rel,
-                                                float inv_count) {
-  const float diff = lv - pv, base = lv - bv;
-  const float me = diff * diff;
-  const float den = base * base + floor;
-  HeadTerms t;
-  t.abs_error = me;
-  t.rel_error = me / den;
-  t.cotangent = ((2.0f * (pv - lv)) * (coef_abs + coef_rel / den)) * inv_count;
-  return t;
-}
-
-// The LDS rows of one workgroup: the plan of loss_grad_kernel / vjp_kernel, then the
-// adjoint of the state and the state gradient of the midpoint evaluation
-struct Rows {
-  float* u;      // [N] the state of the current evaluation
-  float* gdy;    // [N] cotangent of the time derivative; g_s at the end of a product
-  float* gfl;    // [N] flux (forward) / cotangent of the flux (backward)
-  float* pred;   // [N][H] one evaluation's predictions
-  float* gp;     // [N][H] cotangent of the predictions
-  float* gsd;    // [N][H] cotangents of the space derivatives / abs. error terms
-  float* gu;     // [N][H] state gradient (a) + (b) (first N) / rel. error terms
-  float* buf0;   // [N][cmax]
-  float* buf1;   // [N][cmax]
-  float* wl;     // staged 32 x 32 kernels
-  float* lam;    // [N] adjoint of the state
-  float* gmid;   // [N] g_mid
-};
-
-// The vector-Jacobian product of the evaluation whose forward pass has just run
-// (forward_sample: r.u, r.pred, the net output in cur, the pre-activations in zs) with
-// the cotangent in r.gp: the weight gradient is added into slab, the state gradient goes
-// to grad_y [N] (LDS) unless null.  vjp_kernel's backward pass.  Block-wide.
-__device__ __forceinline__ void evaluation_vjp(const TrainParams& p, const Rows& r,
-                                               const float* zs, float* cur, float* nxt,
-                                               float* slab, float* grad_y) {
-  const int tid = threadIdx.x, n = p.N, H = p.H, D = p.D;
-  const bool stencils = p.target == TARGET_COEFFICIENTS;
-  const bool direct_time = p.target == TARGET_TIME_DERIVATIVE;
-  const bool flux_diff = !direct_time && p.conservative;
-  const int gl = p.G / 2;
-  const float* u = r.u;
-  // ---- backward through the equation of motion and the flux difference
-  for (int x = tid; x < n; x += kThreads) r.gdy[x] = r.gp[(size_t)x * H + D];
-  __syncthreads();
-  for (int x = tid; x < n; x += kThreads)
-    r.gfl[x] = flux_diff ? p.inv_dx * (r.gdy[x] - r.gdy[x == 0 ? n - 1 : x - 1]) : r.gdy[x];
-  __syncthreads();
-  // ---- ... the stencils and the projection: d / d net output, into nxt; gs and the
-  // state gradient's term (a)
-  float* gz = nxt;
-  for (int x = tid; x < n; x += kThreads) {
-    if (direct_time) {
-      gz[x] = r.gfl[x];
-      r.gu[x] = 0.0f;
-      continue;
-    }
-    float dv[kMaxDerivs] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int d = 0; d < D; ++d) dv[d] = r.pred[(size_t)x * H + d];
-    r.gu[x] = r.gfl[x] * rhs_state_partial(p.equation, dv);
-    for (int d = 0; d < D; ++d) {
-      const float gs = r.gp[(size_t)x * H + d] +
-                       r.gfl[x] * rhs_partial(p.equation, d, u[x], dv, p.eta);
-      r.gsd[(size_t)x * H + d] = gs;
-      if (p.target == TARGET_SPACE_DERIVATIVES) {
-        gz[(size_t)x * p.C_out + d] = gs;
-      } else if (p.pao == 0) {
-        float mean = 0.0f;
-        if (p.unbiased) {
-          for (int g = 0; g < p.G; ++g) mean += gs * u[wrap(x + g - gl, n)];
-          mean = mean / (float)p.G;
-        }
-        for (int g = 0; g < p.G; ++g)
-          gz[(size_t)x * p.C_out + d * p.G + g] = gs * u[wrap(x + g - gl, n)] - mean;
-      } else {
-        const float* __restrict__ ns = p.nullspace + p.ns_off[d];
-        for (int j = 0; j < p.in_size[d]; ++j) {
-          float acc = 0.0f;
-          for (int g = 0; g < p.G; ++g)
-            acc = fmaf(gs * u[wrap(x + g - gl, n)], ns[j * p.G + g], acc);
-          gz[(size_t)x * p.C_out + p.in_start[d] + j] = acc;
-        }
-      }
-    }
-  }
-  __syncthreads();
-  if (grad_y != nullptr && stencils) {
-    // term (b): point x enters the stencil of x - g + gl as tap g; the coefficients are
-    // re-formed from the net output (cur, still live) exactly as forward_sample forms them
-    const float* net = cur;
-    for (int x = tid; x < n; x += kThreads) {
-      float acc = 0.0f;
-      for (int d = 0; d < D; ++d) {
-        for (int g = 0; g < p.G; ++g) {
-          const int xs = wrap(x - g + gl, n);
-          float coeff;
-          if (p.pao == 0) {
-            float mean = 0.0f;
-            if (p.unbiased) {
-              for (int h = 0; h < p.G; ++h) mean += net[(size_t)xs * p.C_out + d * p.G + h];
-              mean = mean / (float)p.G;
-            }
-            coeff = net[(size_t)xs * p.C_out + d * p.G + g] - mean;
-          } else {
-            const float* __restrict__ ns = p.nullspace + p.ns_off[d];
-            const float* __restrict__ nv = net + (size_t)xs * p.C_out + p.in_start[d];
-            float proj = 0.0f;
-            for (int j = 0; j < p.in_size[d]; ++j) proj = fmaf(nv[j], ns[j * p.G + g], proj);
-            coeff = p.bias[d * p.G + g] + proj;
-          }
-          acc = fmaf(r.gsd[(size_t)xs * H + d], coeff, acc);
-        }
-      }
-      r.gu[x] += acc;
-    }
-    __syncthreads();
-  }
-  // ---- the tower, top down (the net output is no longer needed); term (c) and the
-  // state gradient's store at layer 0
-  tower_backward(p, r.wl, zs, u, gz, cur, slab, true, r.gu, grad_y);
-  __syncthreads();
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(kThreads) void unrolled_loss_grad_kernel(UnrolledParams q) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const TrainParams& p = q.t;
   const int tid = threadIdx.x, n = p.N, H = p.H, D = p.D;
   const int T = q.T, HT = q.HT, E = 2 * T;   // E evaluations: 2 s at y_s, 2 s + 1 at y_mid_s
-  Rows r;
-  r.u = smem;
-  r.gdy = r.u + n;
-  r.gfl = r.gdy + n;
-  r.pred = r.gfl + n;
-  r.gp = r.pred + (size_t)n * H;
-  r.gsd = r.gp + (size_t)n * H;
-  r.gu = r.gsd + (size_t)n * H;
-  r.buf0 = r.gu + (size_t)n * H;
-  r.buf1 = r.buf0 + (size_t)n * p.cmax;
-  r.wl = r.buf1 + (size_t)n * p.cmax;
-  r.lam = r.wl + p.wl_floats;
-  r.gmid = r.lam + n;
+  const Rows r = carve_rows(p, smem, true);
   float* slab = p.ws + (size_t)blockIdx.x * p.slab_stride;
   float* zs = slab + p.n_slab;
   float* st = slab + q.st_off;   // [E][N] stage states
@@ -179,13 +34,7 @@ __global__ __launch_bounds__(kThreads) void unrolled_loss_grad_kernel(UnrolledPa
   const float inv_count = 1.0f / ((float)p.batch * (float)n);
   const float dt = q.dt, half_dt = 0.5f * q.dt;
 
-  for (int i = tid; i < p.n_slab; i += kThreads) slab[i] = 0.0f;
-  for (int l = 0; l < p.L; ++l) {
-    if (p.wl_off[l] < 0) continue;
-    const float* src = p.weights + p.w_off[l];
-    for (int i = tid; i < p.K * 32 * 32; i += kThreads) r.wl[p.wl_off[l] + i] = src[i];
-  }
-  __syncthreads();
+  stage_workgroup(p, slab, p.n_slab, r.wl);
 
   for (int s = blockIdx.x; s < p.batch; s += gridDim.x) {
     const int row = p.sample_index != nullptr ? p.sample_index[s] : s;
@@ -288,7 +137,8 @@ __global__ __launch_bounds__(kThreads) void unrolled_loss_grad_kernel(UnrolledPa
       __syncthreads();
       // g_mid to its own row; g_s to gdy (free once the product has read it); lam_0 is
       // not an output, so the last product skips the state gradient
-      evaluation_vjp(p, r, zs, cur, nxt, slab, mid ? r.gmid : (e > 0 ? r.gdy : nullptr));
+      evaluation_vjp<true>(p, r, zs, cur, nxt, slab, true,
+                     mid ? r.gmid : (e > 0 ? r.gdy : nullptr));
       if (!mid && e > 0) {
         for (int x = tid; x < n; x += kThreads)
           r.lam[x] = ((r.lam[x] + r.gmid[x]) + r.gdy[x]) + gi[(size_t)(step - 1) * n + x];
@@ -298,31 +148,12 @@ __global__ __launch_bounds__(kThreads) void unrolled_loss_grad_kernel(UnrolledPa
   }
 }
 
-// grad[i] = sum over workgroups b (in order) of slab_b[i]; head_means = head sums / (batch N)
-__global__ __launch_bounds__(kThreads) void unrolled_reduce_kernel(UnrolledParams q, int blocks) {
-  const TrainParams& p = q.t;
-  const int first = p.want_grad ? 0 : p.n_weights;
-  const int total = p.n_weights + 2 * q.HT;
-  for (int i = first + blockIdx.x * kThreads + threadIdx.x; i < total; i += gridDim.x * kThreads) {
-    float acc = 0.0f;
-    for (int b = 0; b < blocks; ++b) acc += p.ws[(size_t)b * p.slab_stride + i];
-    if (i < p.n_weights) p.grad[i] = acc;
-    else p.head_means[i - p.n_weights] = acc / ((float)p.batch * (float)p.N);
-  }
-}
-
 hipError_t launch_unrolled_loss_grad(const UnrolledParams& q, int blocks, size_t lds_bytes,
                                      hipStream_t stream) {
-  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(unrolled_loss_grad_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(unrolled_loss_grad_kernel, dim3(blocks), dim3(kThreads), lds_bytes, stream, q);
-  err = hipGetLastError();
-  if (err != hipSuccess) return err;
-  const int total = q.t.n_weights + 2 * q.HT;
-  const int grid = (total + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(unrolled_reduce_kernel, dim3(grid), dim3(kThreads), 0, stream, q, blocks);
-  return hipGetLastError();
+  const TrainParams& p = q.t;
+  return launch_then_sum(reinterpret_cast<const void*>(unrolled_loss_grad_kernel), &q, p, blocks,
+                         lds_bytes, stream, p.want_grad ? 0 : p.n_weights,
+                         p.n_weights + 2 * q.HT);
 }
 
 }  // namespace train
