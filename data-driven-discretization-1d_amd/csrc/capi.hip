@@ -24,6 +24,7 @@
 #include "launch.h"
 #include "launch_weno.h"
 #include "ops.h"
+#include "pack_weights.h"
 #ifdef DDD_PROBES
 #include "probe_kernels.h"
 #endif
@@ -469,426 +470,38 @@ int upload_padded_tables(ddd_model* m, const float* nullspace, const float* bias
   return DDD_OK;
 }
 
-// [rows][64] -> the storage order of rhs_mfma.h load_rows4: four rows to a float4 per
-// lane, rows zero-padded to a multiple of four.
-std::vector<float> quad_rows(const float* rows64, int rows) {
-  std::vector<float> out((size_t)ddd::mfma::padded_rows4(rows) * 64, 0.0f);
-  for (int s = 0; s < rows; ++s)
-    for (int lane = 0; lane < 64; ++lane)
-      out[((size_t)(s >> 2) * 64 + lane) * 4 + (s & 3)] = rows64[(size_t)s * 64 + lane];
-  return out;
-}
-
-// Natural-layout description of the net the MFMA packing reads: the model's own
-// ([K][cin][cout] + bias per layer, DevParams::w_off / b_off) or its zero-padded
-// 5-tap x 32-channel embedding (embed_small_tower).
-struct NetLayout {
-  const float* weights;
-  int w_off[ddd::kMaxLayers], b_off[ddd::kMaxLayers];
-};
-
-// Reorder conv weights into MFMA A-operand order (rhs_mfma.h).
-int pack_mfma_weights(ddd_model* m, const NetLayout& net) {
-  const ddd::DevParams& dp = m->dp;
-  const float* weights = net.weights;
-  const int hidden = dp.L - 2;
-  const int tk = m->tower_k, tcb = m->tower_cb, tc = 32 * tcb;   // the (padded) net: tk taps, tc filters
-  // relu towers run on activations scaled by 2^-kReluShift (dev_params.h: the relu is the
-  // VALU's [0, 1] clamp on a packed add): the input layer's weights and every bias row of
-  // the tower carry `dn`, the output layer's weights `up`.  Exact: powers of two.
-  const bool relu_clamp = dp.act == ddd::ACT_RELU;
-  const float dn = relu_clamp ? std::ldexp(1.0f, -ddd::kReluShift) : 1.0f;
-  const float up = relu_clamp ? std::ldexp(1.0f, ddd::kReluShift) : 1.0f;
-  if (m->big()) {
-    // streamed layouts of rhs_mfma.h: input_layer_big / hidden_layer_stream
-    const int in_steps = (tk + 2) / 2;
-    {
-      const float* w = weights + net.w_off[0];   // [tk][1][tc]
-      const float* b = weights + net.b_off[0];
-      std::vector<float> packed((size_t)tcb * in_steps * 64, 0.0f);
-      for (int h = 0; h < tcb; ++h)
-        for (int s = 0; s < in_steps; ++s)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int k = 2 * s + (lane >> 5), ch = 32 * h + (lane & 31);
-            packed[((size_t)h * in_steps + s) * 64 + lane] =
-                dn * (k < tk ? w[k * tc + ch] : k == tk ? b[ch] : 0.0f);
-          }
-      int rc = upload(packed, &m->d_w_input);
-      if (rc) return rc;
-      m->dp.w_input = m->d_w_input;
-    }
-    if (hidden > 0) {
-      const int groups = tk * tc / 8;   // Tower::kHidGroups
-      const size_t layer_floats = (size_t)groups * tcb * 64 * 4 + (size_t)tcb * 64;
-      std::vector<float> packed((size_t)hidden * layer_floats, 0.0f);
-      for (int l = 0; l < hidden; ++l) {
-        const float* w = weights + net.w_off[l + 1];   // [tk][tc][tc]
-        const float* b = weights + net.b_off[l + 1];
-        float* dst = packed.data() + (size_t)l * layer_floats;
-        for (int g = 0; g < groups; ++g)
-          for (int h = 0; h < tcb; ++h)
-            for (int lane = 0; lane < 64; ++lane)
-              for (int e = 0; e < 4; ++e) {
-                const int s = 4 * g + e;                       // reduction step of this output block
-                const int tap = s / (16 * tcb), cb = (s / 16) % tcb, jj = s % 16;
-                const int cin = 32 * cb + 16 * (lane >> 5) + jj, cout = 32 * h + (lane & 31);
-                dst[(((size_t)g * tcb + h) * 64 + lane) * 4 + e] =
-                    w[((size_t)tap * tc + cin) * tc + cout];
-              }
-        float* bias = dst + (size_t)groups * tcb * 64 * 4;
-        for (int h = 0; h < tcb; ++h)
-          for (int lane = 0; lane < 32; ++lane) bias[h * 64 + lane] = dn * b[32 * h + lane];
-      }
-      int rc = upload(packed, &m->d_w_hidden);
-      if (rc) return rc;
-      m->dp.w_hidden = m->d_w_hidden;
-    }
-  } else {
-  {
-    // input layer 1 -> 32: k = 2 s + (lane >> 5) is the tap, k = 5 the bias
-    const float* w = weights + net.w_off[0];   // [5][1][32]
-    const float* b = weights + net.b_off[0];
-    std::vector<float> packed((size_t)ddd::mfma::kInSteps * 64, 0.0f);
-    for (int s = 0; s < ddd::mfma::kInSteps; ++s)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int k = 2 * s + (lane >> 5), ch = lane & 31;
-        packed[s * 64 + lane] = dn * (k < 5 ? w[k * 32 + ch] : b[ch]);
-      }
-    int rc = upload(quad_rows(packed.data(), ddd::mfma::kInSteps), &m->d_w_input);
-    if (rc) return rc;
-    m->dp.w_input = m->d_w_input;
-  }
-  if (hidden > 0) {
-    std::vector<float> packed((size_t)hidden * ddd::mfma::kHidSteps * 64, 0.0f);
-    for (int h = 0; h < hidden; ++h) {
-      const float* w = weights + net.w_off[h + 1];   // [5][32][32]
-      const float* b = weights + net.b_off[h + 1];
-      float* dst = packed.data() + (size_t)h * ddd::mfma::kHidSteps * 64;
-      for (int s = 0; s < 80; ++s) {
-        const int tap = s / 16, jj = s % 16;
-        for (int lane = 0; lane < 64; ++lane) {
-          const int cin = 16 * (lane >> 5) + jj, cout = lane & 31;
-          dst[s * 64 + lane] = w[(tap * 32 + cin) * 32 + cout];
-        }
-      }
-      for (int lane = 0; lane < 64; ++lane)
-        dst[80 * 64 + lane] = (lane >> 5) == 0 ? dn * b[lane & 31] : 0.0f;
-    }
-    std::vector<float> stored;   // every hidden layer padded on its own (load_hidden)
-    for (int h = 0; h < hidden; ++h) {
-      const std::vector<float> q =
-          quad_rows(packed.data() + (size_t)h * ddd::mfma::kHidSteps * 64, ddd::mfma::kHidSteps);
-      stored.insert(stored.end(), q.begin(), q.end());
-    }
-    int rc = upload(stored, &m->d_w_hidden);
-    if (rc) return rc;
-    m->dp.w_hidden = m->d_w_hidden;
-  }
-  }   // default tower
-  {
-    const int l = dp.L - 1;
-    const int kc = tk * tc;                      // reduction length of the output layer
-    const int fin_k = kc + 1;                    // ... + the bias row (Tower::kFinK)
-    const auto fin_regs = [fin_k](int groups) { return (fin_k * groups + 15) / 16; };
-    const float* w_nat = weights + net.w_off[l];   // [5][32][C_out]
-    const float* b_nat = weights + net.b_off[l];
-    // Fold coeff = bias + net[start:stop] @ nullspace into the output layer:
-    // W'[tap][cin][G d + g] = sum_j W[tap][cin][start_d + j] * ns_d[j][g]
-    // (accumulated in double, rounded once to float32), same for the bias.
-    // The layer then emits the D x G coefficients directly and the epilogue's
-    // projection disappears.  Deviation from the reference's operation order:
-    // O(1 ulp) of the coefficient deltas, far inside the 1e-5 tolerance.
-    // (wf / bf: 16 columns, channel G d + g; D <= 2, G <= 8.)
-    std::vector<float> wf, bf;
-    const bool projected = dp.target == ddd::TARGET_COEFFICIENTS && dp.pao > 0;
-    const bool direct_coeffs = dp.target == ddd::TARGET_COEFFICIENTS && dp.pao <= 0;
-    // the kernels' folded epilogue exists for two derivatives and 6..8 stencil points
-    // (default flavour: channel G d + g of 16) and -- always -- for the wide flavour's
-    // coefficient nets (channel wide_slot(G) d + g of 36, up to three derivatives: the wide
-    // kernels have no projection code at all)
-    const bool wide_fold = m->wide && dp.target == ddd::TARGET_COEFFICIENTS;
-    const int slot = wide_fold ? ddd::mfma::wide_slot(dp.G) : dp.G;
-    const int fold_cols = wide_fold ? ddd::mfma::flavour_net_channels(true) : 16;
-    const bool fold_shape = wide_fold ? dp.D <= ddd::mfma::kWideDerivs
-                                      : dp.D <= 2 && dp.G >= 6 && dp.G <= ddd::kGMax && !m->wide;
-    bool can_fold = projected && fold_shape && (!g_debug.no_fold || wide_fold);
-    if (direct_coeffs && fold_shape) {
-      // the net emits the D x G coefficients themselves (model.py:460-475) in
-      // exactly the folded layer's channel order: nothing to project
-      can_fold = true;
-      wf.assign((size_t)kc * fold_cols, 0.0f);
-      bf.assign(fold_cols, 0.0f);
-      for (int d = 0; d < dp.D; ++d)
-        for (int g = 0; g < dp.G; ++g) {
-          const int c = dp.G * d + g, oc = slot * d + g;
-          for (int row = 0; row < kc; ++row)
-            wf[(size_t)row * fold_cols + oc] = w_nat[(size_t)row * dp.C_out + c];
-          bf[oc] = b_nat[c];
-        }
-    } else if (can_fold) {
-      wf.assign((size_t)kc * fold_cols, 0.0f);
-      bf.assign(fold_cols, 0.0f);
-      for (int d = 0; d < dp.D; ++d)
-        for (int g = 0; g < dp.G; ++g) {
-          const int oc = slot * d + g;
-          for (int row = 0; row < kc; ++row) {
-            double acc = 0.0;
-            for (int j = 0; j < dp.in_size[d]; ++j)
-              acc += (double)w_nat[(size_t)row * dp.C_out + dp.in_start[d] + j] *
-                     (double)dp.ns8[dp.in_start[d] + j][g];
-            wf[(size_t)row * fold_cols + oc] = (float)acc;
-          }
-          // bias row of the folded layer: the accuracy layer's standard
-          // coefficients + the projected conv bias, rounded once
-          double acc = (double)dp.bias8[d][g];
-          for (int j = 0; j < dp.in_size[d]; ++j)
-            acc += (double)b_nat[dp.in_start[d] + j] * (double)dp.ns8[dp.in_start[d] + j][g];
-          bf[oc] = (float)acc;
-        }
-    }
-    // Packing for the 4x4x1 broadcast MFMA (rhs_mfma.h: final_layer4): channels
-    // grouped by four; instruction q = k * groups + grp reads lanes
-    // 4 (q % 16) .. + 3 of weight register q / 16, lane 4 abid + r carrying
-    // channel 4 grp + r; k = (tap, cin) in natural order, k = 160: bias.
-    // `folded`: source = the folded layer (16 columns, channel G d + g), else the
-    // natural one; `renumber`: only the live channels.
-    auto pack4 = [&](int groups, bool folded, bool renumber) {
-      const float* w = folded ? wf.data() : w_nat;
-      const float* b = folded ? bf.data() : b_nat;
-      const int cout_n = folded ? fold_cols : dp.C_out;
-      const int n_ch = folded ? dp.D * dp.G : dp.C_out;
-      std::vector<float> packed4((size_t)ddd::mfma::fin4_regs(4) * 64, 0.0f);
-      for (int k = 0; k < ddd::mfma::kFin4K; ++k)
-        for (int grp = 0; grp < groups; ++grp) {
-          const int q = k * groups + grp;
-          for (int r = 0; r < 4; ++r) {
-            const int ch = 4 * grp + r;
-            int src = ch;
-            if (renumber && ch >= n_ch) continue;   // folded columns are contiguous already
-            if (src >= cout_n) continue;
-            packed4[(size_t)(q / 16) * 64 + 4 * (q % 16) + r] =
-                k < 160 ? up * w[(size_t)k * cout_n + src] : b[src];
-          }
-        }
-      return packed4;
-    };
-    // Run-time-parameterised kernels: only the live channel groups are issued,
-    // as interleaved accumulator chains (rhs_mfma.h: two or three chains run at
-    // 8.1 cycles per MFMA, a lone group at 13.2).  Folding the projection trades the
-    // epilogue's ~C_out x G FMAs (~2.5 units of 161 MFMA slots) for D x G
-    // instead of C_out channels: fold only where the matrix work does not grow
-    // by more than that (the same outcome as rhs_mfma.h: spec_folded for the six
-    // default models, so the two kernel families stay bit-identical).
-    // polynomial_accuracy_order = 0 has nothing to project.
-    const auto issue_cost = [](int groups) { return groups == 1 ? 13.2 : 8.1 * groups; };
-    const int groups_rt_plain = (dp.C_out + 3) / 4;
-    const int groups_rt_folded = ((dp.D - 1) * slot + dp.G + 3) / 4;
-    const bool fold_rt = can_fold && (direct_coeffs || wide_fold ||
-                                      issue_cost(groups_rt_folded) <=
-                                          issue_cost(groups_rt_plain) + 2.5);
-    if (wide_fold && !fold_rt) return DDD_ERR_UNSUPPORTED;   // (decide_mfma admits only what folds)
-    m->dp.folded = fold_rt ? 1 : 0;
-    m->dp.rt_groups = fold_rt ? groups_rt_folded : groups_rt_plain;
-    {
-      const float* w = fold_rt ? wf.data() : w_nat;
-      const float* b = fold_rt ? bf.data() : b_nat;
-      const int cout_n = fold_rt ? fold_cols : dp.C_out;
-      // layout: the head chunk (rt_head_groups: 0, 1 or 3 groups, fin4_regs(head)
-      // rows), then the pairs (fin4_regs(2) rows each); + slack so that the
-      // kernels' fixed-size first fetch (fin4_regs(3) rows) stays inside
-      const int groups = m->dp.rt_groups, head = ddd::mfma::rt_head_groups(groups);
-      const int pair_rows = fin_regs(2), head_rows = fin_regs(head);
-      const int total_rows = head_rows + (groups - head) / 2 * pair_rows + fin_regs(3);
-      std::vector<float> packed((size_t)total_rows * 64, 0.0f);
-      const auto pack_chunk = [&](int row0, int first_group, int ng) {
-        for (int k = 0; k < fin_k; ++k)
-          for (int gi = 0; gi < ng; ++gi) {
-            const int q = k * ng + gi;
-            for (int r = 0; r < 4; ++r) {
-              const int ch = 4 * (first_group + gi) + r;
-              if (ch >= cout_n) continue;
-              packed[((size_t)row0 + q / 16) * 64 + 4 * (q % 16) + r] =
-                  k < kc ? up * w[(size_t)k * cout_n + ch] : b[ch];
-            }
-          }
-      };
-      if (head > 0) pack_chunk(0, 0, head);
-      for (int g0 = head; g0 < groups; g0 += 2)
-        pack_chunk(head_rows + (g0 - head) / 2 * pair_rows, g0, 2);
-      int rc2 = upload(packed, &m->d_w_final4_rt);
-      if (rc2) return rc2;
-      m->dp.w_final4_rt = m->d_w_final4_rt;
-    }
-    int rc = DDD_OK;
-    // specialised kernels: live channels only; folded only where that does not
-    // cost a channel group (same rule as rhs_mfma.h: spec_folded)
-    const int groups_folded = (dp.D * dp.G + 3) / 4, groups_plain = (dp.C_out + 3) / 4;
-    m->spec_folded = can_fold && groups_folded <= groups_plain;
-    m->dp.fin4_groups = m->spec_folded ? groups_folded : groups_plain;
-    if (!m->wide && !m->big()) {   // (the specialised kernels: default tower, not wide)
-      rc = upload(quad_rows(pack4(m->dp.fin4_groups, m->spec_folded, true).data(),
-                            ddd::mfma::fin4_regs(4)),
-                  &m->d_w_final4);
-      if (rc) return rc;
-      m->dp.w_final4 = m->d_w_final4;
-      // the same layer for the split integrators (rhs_mfma.h kSplit): two chunks of
-      // channel groups, each packed on its own and quad-stored in 24 rows
-      {
-        const float* w = m->spec_folded ? wf.data() : w_nat;
-        const float* b = m->spec_folded ? bf.data() : b_nat;
-        const int cout_n = m->spec_folded ? fold_cols : dp.C_out;
-        const int n_ch = m->spec_folded ? dp.D * dp.G : dp.C_out;
-        const int groups = m->dp.fin4_groups, na = (groups + 1) / 2;
-        const int chunk_rows = ddd::mfma::fin4_regs(2);
-        std::vector<float> both;
-        for (int c = 0; c < 2; ++c) {
-          const int g0 = c == 0 ? 0 : na, ng = c == 0 ? na : groups - na;
-          std::vector<float> chunk((size_t)chunk_rows * 64, 0.0f);
-          for (int k = 0; k < ddd::mfma::kFin4K && ng > 0 && ng <= 2; ++k)
-            for (int gi = 0; gi < ng; ++gi) {
-              const int q = k * ng + gi;
-              for (int r = 0; r < 4; ++r) {
-                const int ch = 4 * (g0 + gi) + r;
-                if (ch >= n_ch || ch >= cout_n) continue;
-                chunk[(size_t)(q / 16) * 64 + 4 * (q % 16) + r] =
-                    k < 160 ? up * w[(size_t)k * cout_n + ch] : b[ch];
-              }
-            }
-          const std::vector<float> q4 = quad_rows(chunk.data(), chunk_rows);
-          both.insert(both.end(), q4.begin(), q4.end());
-        }
-        if (groups <= 4) {
-          rc = upload(both, &m->d_w_final4_split);
-          if (rc) return rc;
-          m->dp.w_final4_split = m->d_w_final4_split;
-        }
-      }
-      // ... and the whole net for the integrators on FOUR 16-row wavefronts (rhs_mfma.h
-      // kQuad), every layer as v_mfma_f32_16x16x4_f32 A operands: lane l supplies
-      // W[out = l & 15][reduction slot sg = l >> 4] of a step.  Three-layer nets only
-      // (the per-equation kernels'), <= 16 output channels in the renumbering of w_final4.
-      if (dp.L == 3 && m->dp.fin4_groups <= 4) {
-        using namespace ddd::mfma;
-        const float* w = m->spec_folded ? wf.data() : w_nat;
-        const float* b = m->spec_folded ? bf.data() : b_nat;
-        const int cout_n = m->spec_folded ? fold_cols : dp.C_out;
-        const int n_ch = m->spec_folded ? dp.D * dp.G : dp.C_out;
-        std::vector<float> quad((size_t)kQuadRows * 64, 0.0f);
-        const float* w0 = weights + net.w_off[0];   // [5][1][32]
-        const float* b0 = weights + net.b_off[0];
-        const float* w1 = weights + net.w_off[1];   // [5][32][32]
-        const float* b1 = weights + net.b_off[1];
-        for (int chh = 0; chh < 2; ++chh)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int sg = lane >> 4, cout = 16 * chh + (lane & 15);
-            // input layer: step 0 = taps 0..3, step 1 = tap 4, bias, 0, 0 (input_layer's k order)
-            quad[(size_t)(chh * kQuadInSteps + 0) * 64 + lane] = dn * w0[sg * 32 + cout];
-            quad[(size_t)(chh * kQuadInSteps + 1) * 64 + lane] =
-                sg == 0 ? dn * w0[4 * 32 + cout] : sg == 1 ? dn * b0[cout] : 0.0f;
-            // hidden layer: step 8 tap + i, slot sg -> cin = (sg >> 1) + 16 (sg & 1) + 2 i:
-            // per tap c = 0, 16, 1, 17, ... -- hidden_layer's order (s = 16 tap + jj, half = l >> 5)
-            float* hid = quad.data() + (size_t)(2 * kQuadInSteps + chh * kQuadHidSteps) * 64;
-            for (int s2 = 0; s2 < 40; ++s2) {
-              const int tap = s2 / 8, i = s2 % 8;
-              const int cin = (sg >> 1) + 16 * (sg & 1) + 2 * i;
-              hid[(size_t)s2 * 64 + lane] = w1[(tap * 32 + cin) * 32 + cout];
-            }
-            hid[(size_t)40 * 64 + lane] = sg == 0 ? dn * b1[cout] : 0.0f;
-          }
-        // output layer: step s2, slot sg -> k = 4 s2 + sg in natural order (final_layer4's), k = 160: bias
-        float* fin = quad.data() + (size_t)(2 * kQuadInSteps + 2 * kQuadHidSteps) * 64;
-        for (int s2 = 0; s2 < kQuadFinSteps; ++s2)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int k = 4 * s2 + (lane >> 4), ch = lane & 15;
-            if (ch >= n_ch || ch >= cout_n || k > 160) continue;
-            fin[(size_t)s2 * 64 + lane] = k < 160 ? up * w[(size_t)k * cout_n + ch] : b[ch];
-          }
-        rc = upload(quad, &m->d_w_quad);
-        if (rc) return rc;
-        m->dp.w_quad = m->d_w_quad;
-      }
-      // ... and, for nets of up to 16 filters (embedded here in 32), the packing of rhs_mfma.h
-      // Tile16Tower: the output layer over 5 x 16 + 1 reduction steps, the input and hidden
-      // layers as 16x16x4 A operands.  Source: the embedded net (channels >= 16 are zero there).
-      if (dp.L == 3 && dp.cout[0] <= 16 && m->dp.fin4_groups <= 4) {
-        using namespace ddd::mfma;
-        const float* w1 = weights + net.w_off[1];   // [5][32][32]
-        const float* b1 = weights + net.b_off[1];
-        const float* w = m->spec_folded ? wf.data() : w_nat;
-        const float* b = m->spec_folded ? bf.data() : b_nat;
-        const int cout_n = m->spec_folded ? fold_cols : dp.C_out;
-        const int n_ch = m->spec_folded ? dp.D * dp.G : dp.C_out;
-        const int groups = m->dp.fin4_groups;
-        std::vector<float> fin((size_t)fin4_regs(4) * 64, 0.0f);
-        for (int k = 0; k <= 80; ++k)   // k = 16 tap + cin, 80: bias
-          for (int grp = 0; grp < groups; ++grp) {
-            const int q = k * groups + grp;
-            for (int r = 0; r < 4; ++r) {
-              const int ch = 4 * grp + r;
-              if (ch >= n_ch || ch >= cout_n) continue;
-              fin[(size_t)(q / 16) * 64 + 4 * (q % 16) + r] =
-                  k < 80 ? up * w[(size_t)((k / 16) * 32 + (k % 16)) * cout_n + ch] : b[ch];
-            }
-          }
-        rc = upload(quad_rows(fin.data(), fin4_regs(4)), &m->d_w_final4_half);
-        if (rc) return rc;
-        // the 16x16x4 A operands: lane l = W[out = l & 15][slot l >> 4];
-        // input layer: step 0 = taps 0..3, step 1 = tap 4, bias, 0, 0; hidden layer: step 4 tap + e,
-        // slot sg -> input channel 4 e + sg; step 20: the bias in slot 0
-        const float* w0 = weights + net.w_off[0];   // [5][1][32]
-        const float* b0 = weights + net.b_off[0];
-        std::vector<float> t16((size_t)(kT16InSteps + kT16HidSteps) * 64, 0.0f);
-        for (int lane = 0; lane < 64; ++lane) {
-          const int sg = lane >> 4, cout = lane & 15;
-          t16[(size_t)0 * 64 + lane] = dn * w0[sg * 32 + cout];
-          t16[(size_t)1 * 64 + lane] = sg == 0 ? dn * w0[4 * 32 + cout] : sg == 1 ? dn * b0[cout] : 0.0f;
-          for (int s2 = 0; s2 < 20; ++s2) {
-            const int tap = s2 / 4, e = s2 % 4;
-            t16[(size_t)(kT16InSteps + s2) * 64 + lane] = w1[(tap * 32 + 4 * e + sg) * 32 + cout];
-          }
-          t16[(size_t)(kT16InSteps + 20) * 64 + lane] = sg == 0 ? dn * b1[cout] : 0.0f;
-        }
-        rc = upload(t16, &m->d_w_t16);
-        if (rc) return rc;
-      }
-    }
-  }
-  return DDD_OK;
-}
-
-// Nets between two towers ride the next tower up EXACTLY (rhs_mfma.h: Tower; the
-// default one has 5 taps x 32 channels), embedded with
-// zero weights: a K-tap kernel (K < 5) is the 5-tap kernel whose outer taps are
-// zero (tap k of K sits at offset k - ceil((K-1)/2), the alignment of
-// layers.pad_periodic(center=True), layers.py:76-79), F < 32 filters are 32
-// filters whose extra rows / columns / biases are zero.  fma(0, x, acc) == acc
-// for every finite x, and a padded channel is multiplied by zero weights in the
-// next layer whatever the activation makes of its 0, so the finite results are
-// bit-identical to the unpadded evaluation order-for-order; the matrix work
-// grows by 5/K and (32/F)^2, still an order of magnitude ahead of the generic
-// kernel.  (Algorithmic FLOPs -- ddd_fma_per_point -- keep counting the true net.)
-void embed_tower(const ddd::DevParams& dp, const std::vector<float>& wv, int tower_k,
-                 int tower_c, std::vector<float>* padded, NetLayout* net) {
-  const int k5 = tower_k, f32 = tower_c;       // (the tower's taps and filters)
-  const int shift = (k5 - 1) / 2 - dp.K / 2;   // ceil((k5-1)/2) - ceil((K-1)/2), k5 odd
-  padded->clear();
-  for (int l = 0; l < dp.L; ++l) {
-    const int cin = l == 0 ? 1 : f32;
-    const int cout = l == dp.L - 1 ? dp.C_out : f32;
-    net->w_off[l] = (int)padded->size();
-    padded->resize(padded->size() + (size_t)k5 * cin * cout, 0.0f);
-    net->b_off[l] = (int)padded->size();
-    padded->resize(padded->size() + (size_t)cout, 0.0f);
-    const float* w = wv.data() + dp.w_off[l];
-    const float* b = wv.data() + dp.b_off[l];
-    for (int k = 0; k < dp.K; ++k)
-      for (int ci = 0; ci < dp.cin[l]; ++ci)
-        for (int co = 0; co < dp.cout[l]; ++co)
-          (*padded)[(size_t)net->w_off[l] + ((size_t)(k + shift) * cin + ci) * cout + co] =
-              w[((size_t)k * dp.cin[l] + ci) * dp.cout[l] + co];
-    for (int co = 0; co < dp.cout[l]; ++co) (*padded)[(size_t)net->b_off[l] + co] = b[co];
-  }
-  net->weights = padded->data();
+// Reorder conv weights into MFMA A-operand order: pack_weights.h computes every layout and
+// the folding decisions on the host; here the buffers are uploaded and DevParams written.
+int pack_mfma_weights(ddd_model* m, const ddd::pack::NetLayout& net) {
+  ddd::DevParams& dp = m->dp;
+  ddd::pack::Input in{};
+  in.L = dp.L; in.D = dp.D; in.G = dp.G; in.C_out = dp.C_out; in.cout0 = dp.cout[0];
+  in.act = dp.act; in.target = dp.target; in.pao = dp.pao;
+  in.in_start = dp.in_start; in.in_size = dp.in_size; in.ns8 = dp.ns8; in.bias8 = dp.bias8;
+  in.wide = m->wide; in.tower_k = m->tower_k; in.tower_cb = m->tower_cb;
+  in.no_fold = g_debug.no_fold != 0;
+  in.net = net;
+  const ddd::pack::Packed packed = ddd::pack::pack_weights(in);
+  int rc = upload(packed.w_input, &m->d_w_input);
+  if (!rc) rc = upload(packed.w_hidden, &m->d_w_hidden);
+  if (!rc && packed.unsupported) rc = DDD_ERR_UNSUPPORTED;
+  if (!rc) rc = upload(packed.w_final4_rt, &m->d_w_final4_rt);
+  if (!rc) rc = upload(packed.w_final4, &m->d_w_final4);
+  if (!rc) rc = upload(packed.w_final4_split, &m->d_w_final4_split);
+  if (!rc) rc = upload(packed.w_quad, &m->d_w_quad);
+  if (!rc) rc = upload(packed.w_final4_half, &m->d_w_final4_half);
+  if (!rc) rc = upload(packed.w_t16, &m->d_w_t16);
+  dp.w_input = m->d_w_input;
+  dp.w_hidden = m->d_w_hidden;
+  dp.w_final4_rt = m->d_w_final4_rt;
+  dp.w_final4 = m->d_w_final4;
+  dp.w_final4_split = m->d_w_final4_split;
+  dp.w_quad = m->d_w_quad;
+  dp.folded = packed.folded;
+  dp.rt_groups = packed.rt_groups;
+  dp.fin4_groups = packed.fin4_groups;
+  m->spec_folded = packed.spec_folded;
+  return rc;
 }
 
 // One-layer nets the MFMA-path kernels carry on their VALU route (DevParams::linear_taps).
@@ -921,7 +534,7 @@ void decide_mfma(ddd_model* m) {
     if (dp.target == ddd::TARGET_COEFFICIENTS && dp.pao <= 0 && dp.D > 2) wide = true;
     if (dp.C_out > ddd::kChMax) wide = true;
     // the smallest tower built that holds the net (launch.h: DDD_FOR_EACH_BIG_TOWER + the
-    // default 5 x 32); nets in between are packed zero-padded (embed_tower)
+    // default 5 x 32); nets in between are packed zero-padded (pack_weights.h: embed_tower)
     m->tower_k = dp.K <= 3 ? 3 : dp.K <= 5 ? 5 : 7;
     m->tower_cb = dp.F <= 32 ? 1 : 2;
     if (m->tower_cb == 2 && m->tower_k == 3) m->tower_k = 5;   // (64-filter towers: 5 and 7 taps)
@@ -936,7 +549,7 @@ void decide_mfma(ddd_model* m) {
     if (dp.F > 64) no("filter_size > 64");
     if (dp.K > 7) no("kernel_size > 7");
     if (dp.L < 2) no("fewer than 2 conv layers");
-    // the wide flavour folds every coefficient net into its output layer (pack_mfma_weights):
+    // the wide flavour folds every coefficient net into its output layer (pack_weights.h):
     // three derivatives' worth of register slots; the projection tables hold 24 net channels
     if (wide && dp.target == ddd::TARGET_COEFFICIENTS && dp.D > ddd::mfma::kWideDerivs)
       no("wide stencils / > 16 output channels with four derivatives");
@@ -2096,11 +1709,11 @@ int ddd_model_create(const ddd_config* cfg, const float* weights, size_t n_weigh
         // falls back to it -- N > 256, ddd_set_kernel(generic) -- never runs the
         // padded net; only the MFMA packing sees the embedding)
         std::vector<float> padded;
-        NetLayout net;
+        ddd::pack::NetLayout net;
         net.weights = wv.data();
         for (int l = 0; l < dp.L; ++l) { net.w_off[l] = dp.w_off[l]; net.b_off[l] = dp.b_off[l]; }
         if (dp.K != m->tower_k || dp.F != 32 * m->tower_cb)
-          embed_tower(dp, wv, m->tower_k, 32 * m->tower_cb, &padded, &net);
+          ddd::pack::embed_tower(dp, wv, m->tower_k, 32 * m->tower_cb, &padded, &net);
         rc = pack_mfma_weights(m, net);
       }
     }

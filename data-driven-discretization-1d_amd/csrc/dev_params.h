@@ -3,33 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mfma_layout.h"   // kMaxLayers, kGMax / kGWide, kChMax / kChWide, kReluShift, ACT_*, TARGET_*
+
 namespace ddd {
 
 constexpr int kMaxDerivs = 4;
-constexpr int kMaxLayers = 8;
 constexpr int kMaxStages = 4;
-constexpr int kGMax = 8;      // widest stencil of the default MFMA kernels (and the stream kernel)
-// "wide" run-time-parameterised MFMA kernels (rhs_mfma.h, kWide): stencils up
-// to 12 points and up to 24 output channels -- coefficient_grid_min_size = 9 and
-// polynomial_accuracy_order = 0 with three derivatives (training_test.py:56-57)
-constexpr int kGWide = 12;
-constexpr int kChMax = 16, kChWide = 24;
 constexpr int kTraceSlots = 256;
 constexpr int kWalkTraceRows = 2048;   // rows per launch of the substep-walk trace (probe library)
 constexpr int kInMax = 8;     // widest per-derivative null space (G - rank)
-
-// relu on the MFMA path = the VALU's [0, 1] output clamp on a PACKED add (v_pk_add_f32 x, 0
-// clamp: two accumulator registers per instruction; gfx950 has no packed f32 max), on
-// activations the host scaled by 2^-kReluShift: the input layer's weights and every
-// bias row of the tower carry the factor, the output layer's weights carry its inverse
-// (capi.hip: pack_mfma_weights).  Powers of two commute with every rounding of the fma
-// chains, so the finite results are the bits of max(x, 0) for activations in
-// [2^(-126 + kReluShift), 2^kReluShift] -- beyond 1.8e19 a state has diverged, below
-// 2e-19 an activation contributes nothing float32 can see.  NaN -> 0 like v_max (DX10 clamp):
-// rhs_mfma.h::eval_rhs re-creates the NaNs a propagating relu would have passed on (one
-// v_cmp per evaluation; the rest only when a state holds a NaN).
-// 64 relu instructions per wave-evaluation become 32 (profiles/r5_valu_census.txt).
-constexpr int kReluShift = 64;
 
 // Equation ids: include/ddd1d.h enum ddd_equation.
 enum : int {
@@ -37,10 +19,6 @@ enum : int {
   EQ_KS = 4, EQ_KS_CONS = 5, EQ_BURGERS_GODUNOV = 6, EQ_KDV_GODUNOV = 7,
   EQ_KS_GODUNOV = 8
 };
-enum : int { ACT_NONE = -1, ACT_RELU = 0, ACT_RELU6 = 1, ACT_TANH = 2,
-             ACT_SOFTPLUS = 3, ACT_ELU = 4 };
-enum : int { TARGET_COEFFICIENTS = 0, TARGET_SPACE_DERIVATIVES = 1,
-             TARGET_TIME_DERIVATIVE = 2, TARGET_FLUX = 3 };
 
 struct DevParams {
   // equation + grid

@@ -35,34 +35,13 @@
 #include <utility>
 
 #include "dev_params.h"
+#include "mfma_layout.h"
 
 namespace ddd {
 namespace mfma {
 
 constexpr int kHS = 36;          // padded activation row stride (floats)
-constexpr int kF = 32;           // hidden channels
-constexpr int kKW = 5;           // conv taps
-constexpr int kInSteps = 3;      // (5 taps + bias) / 2
-constexpr int kHidSteps = 81;    // 5*32/2 MFMA steps + 1 bias step
-constexpr int kFin4K = kKW * kF + 1;   // output layer on 4x4x1 MFMAs: 160 reduction steps + bias
 constexpr int kTrigMax = 12;     // 2 * (distinct wavenumbers) kept per lane
-// Flavours of the run-time-parameterised kernels (template parameter kWide):
-// default: stencils <= 8 points, <= 16 output channels; wide: <= 12 points,
-// <= 24 channels of the net, projection always folded into the output layer.
-__host__ __device__ constexpr int flavour_stencil(bool wide) { return wide ? kGWide : kGMax; }
-__host__ __device__ constexpr int flavour_channels(bool wide) { return wide ? kChWide : kChMax; }
-// Output channels the kernels carry in registers.  The wide flavour's output layer is ALWAYS
-// folded (round 5): it emits coefficient g of derivative d as channel kGWide d + g -- slots
-// of twelve, three channel groups per derivative, D <= 3 --, so the epilogue's register
-// indices are compile-time constants and there is no projection left to run there.
-constexpr int kWideDerivs = 3;
-__host__ __device__ constexpr int flavour_net_channels(bool wide) {
-  return wide ? kWideDerivs * kGWide : kChMax;
-}
-// ... coefficient g of derivative d = channel wide_slot(G) d + g: slots of 8 for stencils
-// of up to 8 points, of exactly G above (27 channels = 7 channel groups for 9 points and
-// three derivatives, where slots of 12 would issue 9).
-__host__ __device__ constexpr int wide_slot(int G) { return G <= kGMax ? kGMax : G; }
 // projection tables in LDS: 4 bias rows + one null-space row per output channel (default
 // flavour; the wide one has nothing to project and stages the bias rows -- the fixed
 // stencils -- only: with the 24 null-space rows its 64-row workgroups took 20 808 bytes,
@@ -80,7 +59,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // create_hparams admits, model.py:455-458 builds whatever they say) run on the
 // run-time-parameterised kernels with the layer weights streamed from L2
 // (input_layer_big / hidden_layer_stream below).  Nets in between are embedded with
-// zero weights in the next tower up (capi.hip: embed_tower).
+// zero weights in the next tower up (pack_weights.h: embed_tower).
 template <int kK_, int kCB_>
 struct Tower {
   static constexpr int kK = kK_;                    // conv taps (odd)
@@ -126,7 +105,6 @@ struct Tile16Tower {
   static constexpr int kOperandGroups = kKW * kFinC / 4;
   static constexpr bool kDefault = true, kRolled = false, kTile16 = true;
 };
-constexpr int kT16InSteps = 2, kT16HidSteps = 4 * kKW + 1;   // A-operand rows of DevParams::w_quad in this mode
 // floats of one hidden layer in the streamed layout: [group][out block][lane] float4, then the
 // bias rows [out block][lane]
 template <class TW>
@@ -291,13 +269,6 @@ __host__ __device__ constexpr int spec_fin_channels(int eq) {
   return spec_folded(eq) ? spec_derivs(eq) * spec_stencil(eq) : spec_net_channels(eq);
 }
 __host__ __device__ constexpr int spec_fin_groups(int eq) { return (spec_fin_channels(eq) + 3) / 4; }
-__host__ __device__ constexpr int fin4_regs(int groups) { return (kFin4K * groups + 15) / 16; }
-// Run-time kernels issue their live channel groups as a head chunk followed by
-// pairs: an even count has no head (0), a single group is its own head (1), any
-// other odd count starts with three interleaved groups.
-__host__ __device__ constexpr int rt_head_groups(int groups) {
-  return groups % 2 == 0 ? 0 : groups == 1 ? 1 : 3;
-}
 
 // Entry `s` of a per-stage constant array that sits in the kernel-argument segment
 // (StageConsts): scalar compares + selects on SGPRs instead of an indexed scalar LOAD
@@ -467,7 +438,6 @@ __device__ __forceinline__ void load_rows4(const float* __restrict__ base, int l
     if (4 * k + 3 < NR) w[4 * k + 3] = v.w;
   }
 }
-constexpr int padded_rows4(int rows) { return (rows + 3) / 4 * 4; }
 
 __device__ __forceinline__ void load_hidden(const DevParams& p, int hidden_index,
                                             int lane, float (&w)[kHidSteps]) {
@@ -719,12 +689,10 @@ __device__ __forceinline__ void hidden_layer(const DevParams& p, const Lane& ln,
 //     4 (4 (c >> 4) + (c & 3)) + ((c & 15) >> 2): the B operands of both layers are two
 //     aligned ds_read_b128 per tap (hidden layer, slot sg = l >> 4: blocks (sg & 1, sg >> 1)
 //     and (sg & 1, (sg >> 1) + 2), elements alternating; output layer: blocks (0, sg), (1, sg)).
-// A operands (capi.hip: pack_quad_weights): DevParams::w_quad = [2 ch][2] input rows,
+// A operands (pack_weights.h: pack_quad): DevParams::w_quad = [2 ch][2] input rows,
 // [2 ch][41] hidden rows, [41] output rows of 64 lanes, lane l = W[out = l & 15][slot l >> 4].
 // ---------------------------------------------------------------------------
 #define DDD_MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x4f32((A), (B), (C), 0, 0, 0)
-constexpr int kQuadHidSteps = 41, kQuadFinSteps = 41, kQuadInSteps = 2;
-constexpr int kQuadRows = 2 * kQuadInSteps + 2 * kQuadHidSteps + kQuadFinSteps;   // rows of w_quad (4 + 82 + 41)
 __host__ __device__ constexpr int quad_channel_float(int c) {   // position of channel c in an LDS row
   return 4 * (4 * (c >> 4) + (c & 3)) + ((c & 15) >> 2);
 }
@@ -2010,7 +1978,7 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
     for (int q = 0; q < kGW / 2; ++q) cf2[d][q] = f32x2{0.0f, 0.0f};
   if (kWide) {
     // wide flavour: the output layer emits the coefficients themselves, wide_slot(G)
-    // channels per derivative (capi.hip: pack_mfma_weights folds the projection and the
+    // channels per derivative (pack_weights.h: fold_output_layer folds the projection and the
     // accuracy bias for every wide model).  One wave-uniform branch over the slot width
     // makes every register index a compile-time constant; nothing is left to project.
     if (!fixed && target == TARGET_COEFFICIENTS) {

@@ -1,7 +1,8 @@
 """Lane-level NumPy emulation of the MFMA kernel's data movement (no GPU).
 
-Transcribes, formula by formula, (a) the weight packing of
-csrc/capi.hip::pack_mfma_weights, (b) the operand gathers / result scatters of
+Takes (a) the packed weights from the PRODUCT's packer, csrc/pack_weights.h compiled by
+g++ (oracle/pack_host.cpp: the buffers ddd_model_create uploads, not a transcription of
+them), transcribes (b) the operand gathers / result scatters of
 csrc/rhs_mfma.h (input_layer, hidden_layer, final_layer4) and (c) the CDNA4
 f32 MFMA register layouts the kernels assume
 (cdna_hip_programming.md section 3):
@@ -15,7 +16,9 @@ f32 MFMA register layouts the kernels assume
 and checks that the composition equals the oracle's conv tower.  The layouts
 themselves are verified on hardware by ddd_selftest_mfma_layout.
 """
+import ctypes
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -24,6 +27,66 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'oracle'))
 import oracle  # noqa: E402
+
+_PACK_PATH = os.path.join(ROOT, 'oracle', 'libpackhost.so')
+_BUFFERS = ('w_input', 'w_hidden', 'w_final4_rt', 'w_final4', 'w_final4_split', 'w_quad',
+            'w_final4_half', 'w_t16')
+_ACT = {'relu': 0, 'tanh': 2}                      # mfma_layout.h ACT_*
+_TARGET_COEFFICIENTS, _TARGET_SPACE_DERIVATIVES = 0, 1
+
+
+def pack_net(kernels, biases, taps=5, blocks=1, act='relu', coefficients=None, wide=False):
+  """csrc/pack_weights.h::pack_weights on the net `kernels` / `biases` (float32, layer l:
+  [K][cin][cout]), carried -- embedded where smaller -- in the tower of `taps` taps and
+  32 * blocks filters.  coefficients: None for a direct head (the output layer is packed as
+  it is), or (G, nullspaces, accuracy biases) per derivative for a coefficient net
+  (nullspaces None: polynomial_accuracy_order 0).  Returns the eight buffers (float64 copies
+  of the float32 values; empty where the model has none) and the decisions."""
+  if not os.path.exists(_PACK_PATH):
+    subprocess.run(['make', '-C', os.path.join(ROOT, 'oracle')], check=True, capture_output=True)
+  lib = ctypes.CDLL(_PACK_PATH)
+  assert all(a.dtype == np.float32 for a in list(kernels) + list(biases))
+  c_out = kernels[-1].shape[2]
+  derivs, g, pao, target = 1, 1, 1, _TARGET_SPACE_DERIVATIVES
+  ns8, bias8 = np.zeros((24, 12), np.float32), np.zeros((4, 12), np.float32)   # DevParams::ns8 / bias8
+  in_start, in_size = np.zeros(4, np.int32), np.zeros(4, np.int32)
+  if coefficients is not None:
+    g, nullspaces, acc_biases = coefficients
+    target, derivs, pao = _TARGET_COEFFICIENTS, len(acc_biases), 0 if nullspaces is None else 1
+    start = 0
+    for d in range(derivs if pao else 0):
+      in_start[d], in_size[d] = start, nullspaces[d].shape[0]
+      ns8[start:start + in_size[d], :g] = nullspaces[d]
+      bias8[d, :g] = acc_biases[d]
+      start += in_size[d]
+  cfg = np.array([len(kernels), kernels[0].shape[0], kernels[0].shape[2], c_out, derivs, g,
+                  _ACT[act], target, pao, wide, taps, blocks, 0], np.int32)
+  flat = np.concatenate([np.concatenate([w.reshape(-1), b]) for w, b in zip(kernels, biases)])
+  fptr, iptr = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)
+  out, decisions = {}, np.zeros(5, np.int32)
+  for name in _BUFFERS:
+    buf = np.zeros(0, np.float32)
+    for _ in range(2):   # the length, then the data
+      count = lib.pack_host(cfg.ctypes.data_as(iptr), flat.ctypes.data_as(fptr),
+                            in_start.ctypes.data_as(iptr), in_size.ctypes.data_as(iptr),
+                            ns8.ctypes.data_as(fptr), bias8.ctypes.data_as(fptr), name.encode(),
+                            buf.ctypes.data_as(fptr), buf.size, decisions.ctypes.data_as(iptr))
+      assert count >= 0
+      if count == buf.size:
+        break
+      buf = np.zeros(count, np.float32)
+    out[name] = buf.astype(np.float64)
+  out.update(zip(('folded', 'rt_groups', 'fin4_groups', 'spec_folded', 'unsupported'),
+                 (int(v) for v in decisions)))
+  assert not out['unsupported']
+  return out
+
+
+def unquad(buf, rows):
+  """[rows][64] from the storage order of rhs_mfma.h load_rows4 (row s of lane l at
+  ((s >> 2) * 64 + l) * 4 + (s & 3)): the inverse of pack_weights.h quad_rows."""
+  return buf.reshape(-1, 64, 4).transpose(0, 2, 1).reshape(-1, 64)[:rows]
+
 
 ROWS, HS = 256, 36
 LANES = np.arange(64)
@@ -38,27 +101,6 @@ def mfma32(a, b, acc):
     i = (r & 3) + 8 * (r >> 2) + 4 * (LANES >> 5)
     acc[:, r] += D[i, LANES & 31]
   return acc
-
-
-def pack_input(w, b):          # capi.hip: input layer
-  packed = np.zeros((3, 64))
-  for s in range(3):
-    for lane in range(64):
-      k, ch = 2 * s + (lane >> 5), lane & 31
-      packed[s, lane] = w[k, 0, ch] if k < 5 else b[ch]
-  return packed
-
-
-def pack_hidden(w, b):         # capi.hip: hidden layer
-  packed = np.zeros((81, 64))
-  for s in range(80):
-    tap, jj = s // 16, s % 16
-    for lane in range(64):
-      cin, cout = 16 * (lane >> 5) + jj, lane & 31
-      packed[s, lane] = w[tap, cin, cout]
-  for lane in range(64):
-    packed[80, lane] = b[lane & 31] if (lane >> 5) == 0 else 0.0
-  return packed
 
 
 def tile_src_row(trow, off, n, rows_used):
@@ -78,22 +120,23 @@ def store_tile32(buf, trow, half, acc):
       buf[trow, 8 * qd + 4 * half + c] = acc[:, 4 * qd + c]
 
 
-RELU_SHIFT = 64   # dev_params.h: kReluShift
+RELU_SHIFT = 64   # mfma_layout.h: kReluShift
 
 
-def emulate_tower(un_rows, n, kernels, biases, c_out, relu_shift=RELU_SHIFT):
-  """un_rows: [256] already divided by the std.  Returns net [256, 16].
+def relu(x):
+  """rhs_mfma.h activate16: the VALU's [0, 1] clamp, on activations that travel scaled by
+  2^-RELU_SHIFT -- the packed input-layer weights and every bias row of the tower carry the
+  factor, the output layer's weights its inverse (pack_weights.h)."""
+  return np.clip(x, 0.0, 1.0)
 
-  relu_shift > 0 (the product, dev_params.h kReluShift): activations travel scaled by
-  2^-relu_shift -- input-layer weights and every bias row of the tower carry the factor,
-  the output layer's weights its inverse (capi.hip: pack_mfma_weights) -- and the relu is
-  the VALU's [0, 1] clamp (rhs_mfma.h: activate16); relu_shift = 0: max(x, 0), unscaled."""
+
+def emulate_tower(un_rows, n, packed, num_layers):
+  """un_rows: [256] already divided by the std; packed: pack_net() of a relu net on the
+  default tower.  Returns net [256, 4 * fin4_groups]."""
   rows_used = (ROWS // n) * n
-  dn, up = np.ldexp(1.0, -relu_shift), np.ldexp(1.0, relu_shift)
-  relu = (lambda x: np.clip(x, 0.0, 1.0)) if relu_shift else (lambda x: np.maximum(x, 0.0))
   hA = np.zeros((ROWS, HS))
   hB = np.zeros((ROWS, HS))
-  w_in = pack_input(kernels[0], biases[0]) * dn
+  w_in = unquad(packed['w_input'], 3)
   # ---- input layer -------------------------------------------------------
   for wave in range(4):
     j, half = LANES & 31, LANES >> 5
@@ -108,9 +151,8 @@ def emulate_tower(un_rows, n, kernels, biases, c_out, relu_shift=RELU_SHIFT):
       store_tile32(hA, trow, half, relu(acc))
   src, dst = hA, hB
   # ---- hidden layers -------------------------------------------------------
-  for l in range(1, len(kernels) - 1):
-    w_h = pack_hidden(kernels[l], biases[l])
-    w_h[80] *= dn   # the bias row
+  for l in range(1, num_layers - 1):
+    w_h = unquad(packed['w_hidden'].reshape(num_layers - 2, -1)[l - 1], 81)   # (load_hidden)
     dst[:] = 0
     for wave in range(4):
       j, half = LANES & 31, LANES >> 5
@@ -126,8 +168,8 @@ def emulate_tower(un_rows, n, kernels, biases, c_out, relu_shift=RELU_SHIFT):
         acc = mfma32(w_h[80], np.ones(64), acc)
         store_tile32(dst, trow, half, relu(acc))
     src, dst = dst, src
-  # ---- output layer (run-time-parameterised kernels: 4 padded groups) ---------
-  return emulate_final4(src, n, kernels[-1] * up, biases[-1], c_out, groups=4)
+  # ---- output layer (w_final4: the live channel groups) --------------------------
+  return emulate_final4(src, n, final4_chunks(packed))
 
 
 def test_relu_as_scaled_clamp_keeps_the_bits():
@@ -199,7 +241,7 @@ def test_emulated_tower_matches_oracle(n, num_layers, c_out):
   want = oracle.conv_stack(u, spec)                      # [samples, n, c_out]
   un_rows = np.zeros(ROWS)
   un_rows[:samples * n] = (u / np.float32(0.8)).reshape(-1)
-  net = emulate_tower(un_rows, n, kernels, biases, c_out)
+  net = emulate_tower(un_rows, n, pack_net(kernels, biases), num_layers)
   got = net[:samples * n, :c_out].reshape(samples, n, c_out)
   np.testing.assert_allclose(got, want, rtol=2e-4, atol=2e-5)
   # padded output channels stay exactly zero
@@ -208,30 +250,43 @@ def test_emulated_tower_matches_oracle(n, num_layers, c_out):
 
 # ---------------------------------------------------------------------------
 # Output layer on v_mfma_f32_4x4x1_16b_f32 with the A block broadcast
-# (rhs_mfma.h::final_layer4, capi.hip: "packed4").  Assumed layout (verified
+# (rhs_mfma.h::final_layer4, pack_weights.h: pack_groups4).  Assumed layout (verified
 # on hardware by ddd_selftest_mfma_layout): with cbsz = 4 / abid = b, register
 # r of lane l accumulates A(lane 4 b + r) * B(lane l).
 # ---------------------------------------------------------------------------
-FIN4_K = 161
+def fin_regs(groups, kc=160):
+  """Weight registers of `groups` channel groups issued together: ceil((kc + 1) groups / 16)
+  (mfma_layout.h fin4_regs, rhs_mfma.h fin4_regs_t)."""
+  return ((kc + 1) * groups + 15) // 16
 
 
-def fin4_regs(groups):
-  return (FIN4_K * groups + 15) // 16
+def final4_chunks(packed):
+  """w_final4 (specialised kernels): every live group in ONE chunk.  A chunk is
+  (weight rows [regs][64], first channel group, groups issued together)."""
+  return [(unquad(packed['w_final4'], fin_regs(4)), 0, packed['fin4_groups'])]
 
 
-def pack_final4(w, b, n_ch, groups=None):   # capi.hip: pack4(groups, renumber)
-  groups = groups or (n_ch + 3) // 4
-  packed = np.zeros((fin4_regs(4), 64))
-  wk = w.reshape(160, -1)
-  for k in range(FIN4_K):
-    for grp in range(groups):
-      q = k * groups + grp
-      for r in range(4):
-        ch = 4 * grp + r
-        if ch >= n_ch:
-          continue
-        packed[q // 16, 4 * (q % 16) + r] = wk[k, ch] if k < 160 else b[ch]
-  return packed, groups
+def final4_rt_chunks(packed, kc=160):
+  """w_final4_rt (run-time kernels): the head chunk (mfma_layout.h rt_head_groups: 0, 1 or 3
+  groups), then the pairs."""
+  groups = packed['rt_groups']
+  head = 0 if groups % 2 == 0 else 1 if groups == 1 else 3
+  rows = packed['w_final4_rt'].reshape(-1, 64)
+  chunks = [(rows, 0, head)] if head else []
+  for g0 in range(head, groups, 2):
+    chunks.append((rows[fin_regs(head, kc) + (g0 - head) // 2 * fin_regs(2, kc):], g0, 2))
+  return chunks
+
+
+def read_final4(chunks, kc=160):
+  """The matrix [kc + 1 (last: bias)][channel] the chunks hold: instruction q = k * ng + gi
+  reads channel 4 (first + gi) + r from lane 4 (q % 16) + r of register q / 16."""
+  total = max(g0 + ng for _, g0, ng in chunks)
+  out = np.zeros((kc + 1, 4 * total))
+  for rows, g0, ng in chunks:
+    q = np.arange(kc + 1)[:, None, None] * ng + np.arange(ng)[None, :, None]
+    out[:, 4 * g0:4 * (g0 + ng)] = rows[q // 16, 4 * (q % 16) + np.arange(4)].reshape(kc + 1, -1)
+  return out
 
 
 def mfma4(a, bop, acc, abid):
@@ -240,27 +295,28 @@ def mfma4(a, bop, acc, abid):
   return acc
 
 
-def emulate_final4(src, n, w, b, n_ch, groups=None):
-  """src: [256, 36] hidden activations.  Returns net [256, 4 * groups]."""
+def emulate_final4(src, n, chunks, taps=5, chans=32):
+  """src: [256, chans + 4] hidden activations; chunks: final4_chunks / final4_rt_chunks.
+  Returns net [256, 4 * groups]."""
   rows_used = (ROWS // n) * n
-  packed, groups = pack_final4(w, b, n_ch, groups)
-  out = np.zeros((ROWS, 4 * groups))
+  left, per_tap, kc = taps // 2, chans // 4, taps * chans
+  out = np.zeros((ROWS, 4 * max(g0 + ng for _, g0, ng in chunks)))
   for wave in range(4):
     row = wave * 64 + LANES
-    acc = [np.zeros((64, 4)) for _ in range(groups)]
-    for og in range(40):
-      tap, c4 = og // 8, og % 8
-      rows = tile_src_row(row, tap - 2, n, rows_used)
-      for e in range(4):
-        bop = src[rows, 4 * c4 + e]
-        for grp in range(groups):
-          q = (og * 4 + e) * groups + grp
-          acc[grp] = mfma4(packed[q // 16], bop, acc[grp], q % 16)
-    for grp in range(groups):
-      q = 160 * groups + grp
-      acc[grp] = mfma4(packed[q // 16], np.ones(64), acc[grp], q % 16)
-    for grp in range(groups):
-      out[row, 4 * grp:4 * grp + 4] = acc[grp]
+    for packed, g0, ng in chunks:
+      acc = [np.zeros((64, 4)) for _ in range(ng)]
+      for og in range(taps * per_tap):
+        tap, c4 = og // per_tap, og % per_tap
+        rows = tile_src_row(row, tap - left, n, rows_used)
+        for e in range(4):
+          bop = src[rows, 4 * c4 + e]
+          for gi in range(ng):
+            q = (og * 4 + e) * ng + gi
+            acc[gi] = mfma4(packed[q // 16], bop, acc[gi], q % 16)
+      for gi in range(ng):
+        q = kc * ng + gi
+        acc[gi] = mfma4(packed[q // 16], np.ones(64), acc[gi], q % 16)
+        out[row, 4 * (g0 + gi):4 * (g0 + gi) + 4] = acc[gi]
   return out
 
 
@@ -268,17 +324,20 @@ def emulate_final4(src, n, w, b, n_ch, groups=None):
                                     (100, 9)])
 def test_emulated_final4_matches_direct_conv(n, n_ch):
   rs = np.random.RandomState(n + n_ch)
-  w = rs.randn(5, 32, n_ch) * 0.3
-  b = rs.randn(n_ch) * 0.1
+  # (rounded to float32, the packer's type, on both sides: the tolerance keeps its meaning)
+  w = (rs.randn(5, 32, n_ch) * 0.3).astype(np.float32)
+  b = (rs.randn(n_ch) * 0.1).astype(np.float32)
+  # a two-layer tanh net (no relu scaling) whose output layer is (w, b); the input layer is not run
+  packed = pack_net([np.zeros((5, 1, 32), np.float32), w], [np.zeros(32, np.float32), b], act='tanh')
   samples = ROWS // n
   h = rs.randn(samples, n, 32)
   src = np.zeros((ROWS, HS))
   src[:samples * n, :32] = h.reshape(-1, 32)
   src[:, 32:] = 7.0   # row padding (forcing trig table in the kernel): never read
-  got = emulate_final4(src, n, w, b, n_ch)[:samples * n].reshape(samples, n, -1)
+  got = emulate_final4(src, n, final4_chunks(packed))[:samples * n].reshape(samples, n, -1)
   want = np.zeros((samples, n, n_ch))
   for tap in range(5):
-    want += np.einsum('bxc,cf->bxf', np.roll(h, 2 - tap, axis=1), w[tap])
+    want += np.einsum('bxc,cf->bxf', np.roll(h, 2 - tap, axis=1), w[tap].astype(np.float64))
   want += b
   np.testing.assert_allclose(got[..., :n_ch], want, rtol=1e-12, atol=1e-12)
   assert np.all(got[..., n_ch:] == 0)
@@ -317,66 +376,20 @@ def test_three_instruction_division_equals_ieee_division():
 
 # ---------------------------------------------------------------------------
 # Towers with streamed weights (rhs_mfma.h Tower<K, CB>: input_layer_big,
-# hidden_layer_stream, final_layer4<NG, TW>; capi.hip pack_mfma_weights `big` branch
-# + embed_tower): K taps, CB blocks of 32 channels, activations in rows of 32 CB + 4.
+# hidden_layer_stream, final_layer4<NG, TW>; pack_weights.h pack_input_stream /
+# pack_hidden_stream + embed_tower): K taps, CB blocks of 32 channels, activations in rows of
+# 32 CB + 4.
 # ---------------------------------------------------------------------------
-def pack_input_big(w, b, taps, blocks):          # [h][s][lane]
-  steps = (taps + 2) // 2
-  packed = np.zeros((blocks, steps, 64))
-  for h in range(blocks):
-    for s in range(steps):
-      for lane in range(64):
-        k, ch = 2 * s + (lane >> 5), 32 * h + (lane & 31)
-        packed[h, s, lane] = w[k, 0, ch] if k < taps else (b[ch] if k == taps else 0.0)
-  return packed
-
-
-def pack_hidden_stream(w, b, taps, blocks):      # [group][block][lane][4] + bias [block][lane]
-  chans = 32 * blocks
-  groups = taps * chans // 8
-  packed = np.zeros((groups, blocks, 64, 4))
-  for g in range(groups):
-    for h in range(blocks):
-      for lane in range(64):
-        for e in range(4):
-          s = 4 * g + e
-          tap, cb, jj = s // (16 * blocks), (s // 16) % blocks, s % 16
-          cin, cout = 32 * cb + 16 * (lane >> 5) + jj, 32 * h + (lane & 31)
-          packed[g, h, lane, e] = w[tap, cin, cout]
-  bias = np.zeros((blocks, 64))
-  for h in range(blocks):
-    bias[h, :32] = b[32 * h:32 * h + 32]
-  return packed, bias
-
-
-def embed(kernels, biases, taps, chans):         # capi.hip: embed_tower
-  out_k, out_b = [], []
-  for l, (w, b) in enumerate(zip(kernels, biases)):
-    k_true = w.shape[0]
-    shift = (taps - 1) // 2 - k_true // 2
-    cin = 1 if l == 0 else chans
-    cout = w.shape[2] if l == len(kernels) - 1 else chans
-    wp = np.zeros((taps, cin, cout), w.dtype)
-    wp[shift:shift + k_true, :w.shape[1], :w.shape[2]] = w
-    bp = np.zeros(cout, b.dtype)
-    bp[:b.shape[0]] = b
-    out_k.append(wp)
-    out_b.append(bp)
-  return out_k, out_b
-
-
-def emulate_big_tower(un_rows, n, kernels, biases, taps, blocks, groups):
+def emulate_big_tower(un_rows, n, packed, num_layers, taps, blocks):
   """One-wave geometry generalised to 256 rows (four wavefronts): the operand
-  gathers of input_layer_big / hidden_layer_stream / final_layer4<NG, TW>."""
+  gathers of input_layer_big / hidden_layer_stream / final_layer4<NG, TW> (the run-time
+  kernels' chunks) over pack_net()'s streamed buffers of a relu net."""
   chans, hs, left = 32 * blocks, 32 * blocks + 4, taps // 2
   rows_used = (ROWS // n) * n
-  # (relu = the [0, 1] clamp on activations scaled by 2^-RELU_SHIFT, as in emulate_tower)
-  dn, up = np.ldexp(1.0, -RELU_SHIFT), np.ldexp(1.0, RELU_SHIFT)
-  relu = lambda x: np.clip(x, 0.0, 1.0)
   bufs = [np.zeros((ROWS, hs)), np.zeros((ROWS, hs))]
   j, half = LANES & 31, LANES >> 5
-  w_in = pack_input_big(kernels[0], biases[0], taps, blocks) * dn
   steps = (taps + 2) // 2
+  w_in = packed['w_input'].reshape(blocks, steps, 64)              # [h][s][lane]
   for wave in range(4):
     for t in range(2):
       trow = wave * 64 + t * 32 + j
@@ -396,21 +409,24 @@ def emulate_big_tower(un_rows, n, kernels, biases, taps, blocks, groups):
           for c in range(4):
             bufs[0][trow, 32 * h + 8 * qd + 4 * half + c] = relu(acc)[:, 4 * qd + c]
   src, dst = bufs
-  for l in range(1, len(kernels) - 1):
-    packed, bias = pack_hidden_stream(kernels[l], biases[l], taps, blocks)
-    bias = bias * dn
+  groups = taps * chans // 8
+  for l in range(1, num_layers - 1):
+    # [group][block][lane][4] + bias [block][lane] (rhs_mfma.h stream_layer_floats)
+    layer = packed['w_hidden'].reshape(num_layers - 2, -1)[l - 1]
+    weights = layer[:groups * blocks * 256].reshape(groups, blocks, 64, 4)
+    bias = layer[groups * blocks * 256:].reshape(blocks, 64)
     dst[:] = 0
     for wave in range(4):
       for t in range(2):
         trow = wave * 64 + t * 32 + j
         acc = [np.zeros((64, 16)) for _ in range(blocks)]
-        for g in range(packed.shape[0]):
+        for g in range(groups):
           tap, cb, quad = g // (4 * blocks), (g // 4) % blocks, g % 4
           rows = tile_src_row(trow, tap - left, n, rows_used)
           for e in range(4):
             bop = src[rows, 32 * cb + 16 * half + 4 * quad + e]
             for h in range(blocks):
-              acc[h] = mfma32(packed[g, h, :, e], bop, acc[h])
+              acc[h] = mfma32(weights[g, h, :, e], bop, acc[h])
         for h in range(blocks):
           acc[h] = mfma32(bias[h], np.ones(64), acc[h])
           for qd in range(4):
@@ -418,36 +434,7 @@ def emulate_big_tower(un_rows, n, kernels, biases, taps, blocks, groups):
               dst[trow, 32 * h + 8 * qd + 4 * half + c] = relu(acc[h])[:, 4 * qd + c]
     src, dst = dst, src
   # output layer: k = tap * chans + c in natural order, K C + 1 reduction steps
-  w, b = kernels[-1], biases[-1]
-  n_ch, kc = w.shape[2], taps * chans
-  fin_k = kc + 1
-  packed = np.zeros(((fin_k * groups + 15) // 16, 64))
-  wk = w.reshape(kc, n_ch)
-  for k in range(fin_k):
-    for grp in range(groups):
-      q = k * groups + grp
-      for r in range(4):
-        ch = 4 * grp + r
-        if ch < n_ch:
-          packed[q // 16, 4 * (q % 16) + r] = up * wk[k, ch] if k < kc else b[ch]
-  out = np.zeros((ROWS, 4 * groups))
-  per_tap = chans // 4
-  for wave in range(4):
-    row = wave * 64 + LANES
-    acc = [np.zeros((64, 4)) for _ in range(groups)]
-    for og in range(taps * per_tap):
-      tap, c4 = og // per_tap, og % per_tap
-      rows = tile_src_row(row, tap - left, n, rows_used)
-      for e in range(4):
-        bop = src[rows, 4 * c4 + e]
-        for grp in range(groups):
-          q = (og * 4 + e) * groups + grp
-          acc[grp] = mfma4(packed[q // 16], bop, acc[grp], q % 16)
-    for grp in range(groups):
-      q = kc * groups + grp
-      acc[grp] = mfma4(packed[q // 16], np.ones(64), acc[grp], q % 16)
-      out[row, 4 * grp:4 * grp + 4] = acc[grp]
-  return out
+  return emulate_final4(src, n, final4_rt_chunks(packed, taps * chans), taps, chans)
 
 
 @pytest.mark.parametrize('n,num_layers,c_out,k_true,f_true,taps,blocks', [
@@ -470,36 +457,31 @@ def test_emulated_streamed_towers_match_oracle(n, num_layers, c_out, k_true, f_t
   want = oracle.conv_stack(u, spec)                      # the TRUE net
   un_rows = np.zeros(ROWS)
   un_rows[:samples * n] = (u / np.float32(0.8)).reshape(-1)
-  pk, pb = embed(kernels, biases, taps, 32 * blocks)
-  groups = (c_out + 3) // 4
-  net = emulate_big_tower(un_rows, n, pk, pb, taps, blocks, groups)
+  packed = pack_net(kernels, biases, taps, blocks)   # (embeds the net in the tower)
+  net = emulate_big_tower(un_rows, n, packed, num_layers, taps, blocks)
   got = net[:samples * n, :c_out].reshape(samples, n, c_out)
   np.testing.assert_allclose(got, want, rtol=2e-4, atol=2e-5)
   assert np.all(net[:samples * n, c_out:] == 0)
 
 
 def wide_slot(g):
-  """rhs_mfma.h: wide_slot -- channels per derivative of the wide flavour's folded output layer."""
+  """mfma_layout.h: wide_slot -- channels per derivative of the wide flavour's folded output layer."""
   return 8 if g <= 8 else g
 
 
-def fold_wide_output_layer(w_nat, b_nat, nullspaces, acc_biases, g):
-  """capi.hip::pack_mfma_weights, wide flavour (always folded): output channel
-  wide_slot(G) d + g' of the folded layer = sum_j W[:, start_d + j] * nullspace_d[j, g']
-  (float64 accumulation, rounded once), bias row = accuracy bias + projected conv bias."""
-  kc, slot = w_nat.shape[0], wide_slot(g)
-  cols = 36
-  wf, bf = np.zeros((kc, cols), np.float32), np.zeros(cols, np.float32)
-  start = 0
-  for d, (ns, ab) in enumerate(zip(nullspaces, acc_biases)):
-    if ns is None:   # polynomial_accuracy_order 0: channel G d + g' IS the coefficient
-      wf[:, slot * d:slot * d + g] = w_nat[:, g * d:g * d + g]
-      bf[slot * d:slot * d + g] = b_nat[g * d:g * d + g]
-      continue
-    stop = start + ns.shape[0]
-    wf[:, slot * d:slot * d + g] = (w_nat[:, start:stop].astype(np.float64) @ ns.astype(np.float64)).astype(np.float32)
-    bf[slot * d:slot * d + g] = (ab.astype(np.float64) + b_nat[start:stop].astype(np.float64) @ ns.astype(np.float64)).astype(np.float32)
-    start = stop
+def folded_wide_output_layer(w_nat, b_nat, nullspaces, acc_biases, g):
+  """The output layer [kc][36] / bias [36] of a wide-flavour net as pack_weights.h folds it
+  (fold_output_layer; the wide flavour always folds), read back from the packed w_final4_rt of a
+  two-layer tanh net (no relu scaling) whose output layer is (w_nat, b_nat).
+  nullspaces[d] None: polynomial_accuracy_order 0."""
+  kc, c_out = w_nat.shape
+  packed = pack_net([np.zeros((5, 1, 32), np.float32), w_nat.reshape(5, 32, c_out)],
+                    [np.zeros(32, np.float32), b_nat], act='tanh', wide=True,
+                    coefficients=(g, None if nullspaces[0] is None else nullspaces, acc_biases))
+  assert packed['folded']
+  layer = read_final4(final4_rt_chunks(packed)).astype(np.float32)   # the channel groups the kernel issues
+  wf, bf = np.zeros((kc, 36), np.float32), np.zeros(36, np.float32)
+  wf[:, :layer.shape[1]], bf[:layer.shape[1]] = layer[:kc], layer[kc]
   return wf, bf
 
 
@@ -522,7 +504,7 @@ def test_wide_fold_equals_projection(g, free, direct):
   else:
     nullspaces = [rs.randn(f, g).astype(np.float32) for f in free]
     acc_biases = [rs.randn(g).astype(np.float32) for _ in free]
-  wf, bf = fold_wide_output_layer(w_nat, b_nat, nullspaces, acc_biases, g)
+  wf, bf = folded_wide_output_layer(w_nat, b_nat, nullspaces, acc_biases, g)
   got = hidden.astype(np.float64) @ wf.astype(np.float64) + bf
   net = hidden.astype(np.float64) @ w_nat.astype(np.float64) + b_nat
   slot, start = wide_slot(g), 0
@@ -544,8 +526,9 @@ def test_wide_fold_equals_projection(g, free, direct):
 # Four 16-row wavefronts per 64-row group (rhs_mfma.h kQuad): every layer on
 # v_mfma_f32_16x16x4_f32 -- lane l supplies A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15];
 # register r of lane l holds D[4 (l >> 4) + r][l & 15] (cdna_hip_programming.md section 3).
-# Transcribes capi.hip's quad packing, rhs_mfma.h's lane_offsets (kWR == 16) and
-# input_layer_quad / hidden_layer_quad / final_layer_quad.
+# Transcribes rhs_mfma.h's lane_offsets (kWR == 16) and input_layer_quad / hidden_layer_quad /
+# final_layer_quad over the shipped w_quad rows (pack_weights.h pack_quad: [2][2] input,
+# [2][41] hidden, [41] output rows x 64 lanes).
 # ---------------------------------------------------------------------------
 def mfma16(a, b, acc):
   A = a.reshape(4, 16).T.astype(np.float64)      # [i, k]
@@ -560,35 +543,10 @@ def quad_channel_float(c):     # rhs_mfma.h: position of channel c in an LDS row
   return 4 * (4 * (c >> 4) + (c & 3)) + ((c & 15) >> 2)
 
 
-def pack_quad(kernels, biases, w_out, b_out, n_ch, dn, up):
-  """capi.hip: the w_quad rows ([2][2] input, [2][41] hidden, [41] output) x 64 lanes."""
-  w0, b0, w1, b1 = kernels[0], biases[0], kernels[1], biases[1]
-  rows = np.zeros((4 + 82 + 41, 64))
-  for chh in range(2):
-    for lane in range(64):
-      sg, cout = lane >> 4, 16 * chh + (lane & 15)
-      rows[chh * 2 + 0, lane] = dn * w0[sg, 0, cout]
-      rows[chh * 2 + 1, lane] = dn * w0[4, 0, cout] if sg == 0 else dn * b0[cout] if sg == 1 else 0.0
-      for s2 in range(40):
-        tap, i = s2 // 8, s2 % 8
-        cin = (sg >> 1) + 16 * (sg & 1) + 2 * i
-        rows[4 + chh * 41 + s2, lane] = w1[tap, cin, cout]
-      rows[4 + chh * 41 + 40, lane] = dn * b1[cout] if sg == 0 else 0.0
-  w_flat = w_out.reshape(160, -1)
-  for s2 in range(41):
-    for lane in range(64):
-      k, ch = 4 * s2 + (lane >> 4), lane & 15
-      if ch >= n_ch or k > 160:
-        continue
-      rows[4 + 82 + s2, lane] = up * w_flat[k, ch] if k < 160 else b_out[ch]
-  return rows
-
-
-def emulate_tower_quad(un64, n, kernels, biases, n_ch, relu_shift=RELU_SHIFT):
-  """One 64-row group on four wavefronts.  un64: [64] = u / std.  Returns net [64, 16]."""
-  dn, up = np.ldexp(1.0, -relu_shift), np.ldexp(1.0, relu_shift)
-  relu = (lambda x: np.clip(x, 0.0, 1.0)) if relu_shift else (lambda x: np.maximum(x, 0.0))
-  wq = pack_quad(kernels, biases, kernels[2], biases[2], n_ch, dn, up)
+def emulate_tower_quad(un64, n, packed):
+  """One 64-row group on four wavefronts.  un64: [64] = u / std; packed: pack_net() of a
+  three-layer relu net.  Returns net [64, 16]."""
+  wq = packed['w_quad'].reshape(4 + 82 + 41, 64)
   hA, hB = np.full((64, HS), np.nan), np.full((64, HS), np.nan)
   sg, j16 = LANES >> 4, LANES & 15
 
@@ -653,7 +611,8 @@ def test_quad_flavour_data_movement(n, c_out):
   samples = 64 // n
   u = rs.randn(samples, n).astype(np.float32)
   un = (u / np.float32(0.8)).reshape(-1).astype(np.float64)
-  got = emulate_tower_quad(un, n, kernels, biases, c_out)
+  packed = pack_net(kernels, biases)
+  got = emulate_tower_quad(un, n, packed)
   spec = dict(standard_deviation=0.8, conv_kernels=kernels, conv_biases=biases,
               num_layers=3, nonlinearity='relu')
   want = oracle.conv_stack(u, spec).reshape(64, c_out)
@@ -662,7 +621,7 @@ def test_quad_flavour_data_movement(n, c_out):
   # against the one-wavefront emulation (float64 both, different association only)
   un_rows = np.zeros(ROWS)
   un_rows[:64] = un
-  one = emulate_tower(un_rows, n, kernels, biases, c_out)[:64]
+  one = emulate_tower(un_rows, n, packed, 3)[:64]
   np.testing.assert_allclose(got[:, :c_out], one[:, :c_out], rtol=1e-9, atol=1e-12)
 
 
@@ -684,33 +643,17 @@ def test_quad_flavour_reduction_order_is_the_one_wavefront_kernels():
 # ---------------------------------------------------------------------------
 # Nets of up to 16 filters on 16-channel tiles (rhs_mfma.h Tile16Tower, round 6): ONE wavefront
 # per 64-row group, every layer of the tower on v_mfma_f32_16x16x4_f32, four position tiles.
-# Transcribes capi.hip's d_w_t16 / d_w_final4_half packing, lane_offsets<..., kTile16>,
-# input_layer_t16 / hidden_layer_t16 / final_layer4_t16.
+# Transcribes lane_offsets<..., kTile16> and input_layer_t16 / hidden_layer_t16 /
+# final_layer4_t16 over the shipped w_t16 ([2] input + [21] hidden rows x 64 lanes) and
+# w_final4_half (pack_weights.h), packed from the net EMBEDDED in 32 filters.
 # ---------------------------------------------------------------------------
 def t16_channel_float(c):      # position of channel c (< 16) in an LDS row
   return 4 * (c & 3) + (c >> 2)
 
 
-def pack_t16(kernels, biases, dn):
-  """capi.hip: [2] input + [21] hidden rows x 64 lanes from the net EMBEDDED in 32 filters."""
-  w0, b0, w1, b1 = kernels[0], biases[0], kernels[1], biases[1]
-  rows = np.zeros((2 + 21, 64))
-  for lane in range(64):
-    sg, cout = lane >> 4, lane & 15
-    rows[0, lane] = dn * w0[sg, 0, cout]
-    rows[1, lane] = dn * w0[4, 0, cout] if sg == 0 else dn * b0[cout] if sg == 1 else 0.0
-    for s2 in range(20):
-      tap, e = s2 // 4, s2 % 4
-      rows[2 + s2, lane] = w1[tap, 4 * e + sg, cout]
-    rows[2 + 20, lane] = dn * b1[cout] if sg == 0 else 0.0
-  return rows
-
-
-def emulate_tower_t16(un64, n, kernels, biases, n_ch, relu_shift=RELU_SHIFT):
-  """kernels / biases: the net embedded in 5 taps x 32 filters (channels >= 16 zero)."""
-  dn, up = np.ldexp(1.0, -relu_shift), np.ldexp(1.0, relu_shift)
-  relu = (lambda x: np.clip(x, 0.0, 1.0)) if relu_shift else (lambda x: np.maximum(x, 0.0))
-  wq = pack_t16(kernels, biases, dn)
+def emulate_tower_t16(un64, n, packed, n_ch):
+  """packed: pack_net() of a three-layer relu net of up to 16 filters."""
+  wq = packed['w_t16'].reshape(2 + 21, 64)
   hA, hB = np.full((64, HS), np.nan), np.full((64, HS), np.nan)
   sg, j16 = LANES >> 4, LANES & 15
 
@@ -744,7 +687,8 @@ def emulate_tower_t16(un64, n, kernels, biases, n_ch, relu_shift=RELU_SHIFT):
     store16(hB, trow, relu(acc))
   # output layer on the 4x4x1 MFMAs, lane == row: four float4 blocks per tap row, channels
   # picked in natural order: channel c = element (c >> 2) of block (c & 3)
-  w_flat = kernels[2].reshape(5, 32, -1)
+  # (w_final4_half: reduction step k = 16 tap + c, k = 80 the bias)
+  w_half = read_final4([(unquad(packed['w_final4_half'], fin_regs(4)), 0, packed['fin4_groups'])], 80)
   net = np.zeros((64, 16))
   rows64 = np.arange(64)
   for ch in range(n_ch):
@@ -752,8 +696,8 @@ def emulate_tower_t16(un64, n, kernels, biases, n_ch, relu_shift=RELU_SHIFT):
     for tap in range(5):
       src = tap_row(rows64, tap - 2)
       for c in range(16):
-        acc = acc + up * w_flat[tap, c, ch] * hB[src, 4 * (c & 3) + (c >> 2)]
-    net[:, ch] = acc + biases[2][ch]
+        acc = acc + w_half[16 * tap + c, ch] * hB[src, 4 * (c & 3) + (c >> 2)]
+    net[:, ch] = acc + w_half[80, ch]
   return net
 
 
@@ -765,25 +709,18 @@ def test_tile16_data_movement(n, filters, c_out):
   true_shapes = [(5, 1, filters), (5, filters, filters), (5, filters, c_out)]
   kernels = [rs.randn(*s).astype(np.float32) * 0.3 for s in true_shapes]
   biases = [rs.randn(s[2]).astype(np.float32) * 0.1 for s in true_shapes]
-  emb_k = [np.zeros((5, 1, 32), np.float32), np.zeros((5, 32, 32), np.float32),
-           np.zeros((5, 32, c_out), np.float32)]
-  emb_b = [np.zeros(32, np.float32), np.zeros(32, np.float32), biases[2]]
-  emb_k[0][:, :, :filters] = kernels[0]
-  emb_k[1][:, :filters, :filters] = kernels[1]
-  emb_k[2][:, :filters, :] = kernels[2]
-  emb_b[0][:filters] = biases[0]
-  emb_b[1][:filters] = biases[1]
   samples = 64 // n
   u = rs.randn(samples, n).astype(np.float32)
   un = (u / np.float32(0.8)).reshape(-1).astype(np.float64)
-  got = emulate_tower_t16(un, n, emb_k, emb_b, c_out)
+  packed = pack_net(kernels, biases)   # (embeds the TRUE net as ddd_model_create does)
+  got = emulate_tower_t16(un, n, packed, c_out)
   spec = dict(standard_deviation=0.8, conv_kernels=kernels, conv_biases=biases,
               num_layers=3, nonlinearity='relu')
   want = oracle.conv_stack(u, spec).reshape(64, c_out)
   np.testing.assert_allclose(got[:, :c_out], want, rtol=2e-4, atol=2e-5)
   un_rows = np.zeros(ROWS)
   un_rows[:64] = un
-  one = emulate_tower(un_rows, n, emb_k, emb_b, c_out)[:64]
+  one = emulate_tower(un_rows, n, packed, 3)[:64]
   np.testing.assert_allclose(got[:, :c_out], one[:, :c_out], rtol=1e-9, atol=1e-12)
 
 
