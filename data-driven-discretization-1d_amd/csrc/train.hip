@@ -9,7 +9,9 @@
 namespace ddd {
 namespace train {
 
-__global__ __launch_bounds__(kThreads) void loss_grad_kernel(TrainParams p) {
+// kCoefTable: the loss constants from p.coef_table (head_terms_of, train_device.h)
+template <bool kCoefTable>
+__device__ __forceinline__ void loss_grad_body(const TrainParams& p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, n = p.N, H = p.H;
   const Rows r = carve_rows(p, smem, false);
@@ -47,8 +49,9 @@ __global__ __launch_bounds__(kThreads) void loss_grad_kernel(TrainParams p) {
     for (int i = tid; i < n * H; i += kThreads) {
       const int h = i % H;
       const float pv = r.pred[i];
-      const HeadTerms t = head_terms(pv, p.labels[loff + i], p.baseline[loff + i], p.floor[h],
-                                     p.coef_abs[h], p.coef_rel[h], inv_count);
+      const HeadTerms t = head_terms_of<kCoefTable>(p, p.floor, p.coef_abs, p.coef_rel, H, h, pv,
+                                                    p.labels[loff + i], p.baseline[loff + i],
+                                                    inv_count);
       em[i] = t.abs_error;
       er[i] = t.rel_error;
       r.gp[i] = t.cotangent;
@@ -73,6 +76,14 @@ __global__ __launch_bounds__(kThreads) void loss_grad_kernel(TrainParams p) {
   }
 }
 
+__global__ __launch_bounds__(kThreads) void loss_grad_kernel(TrainParams p) {
+  loss_grad_body<false>(p);
+}
+
+__global__ __launch_bounds__(kThreads) void loss_grad_table_kernel(TrainParams p) {
+  loss_grad_body<true>(p);
+}
+
 // out[i] = sum over workgroups b (in order) of ws[b stride + i] for first <= i < total:
 // grad below n_weights, behind it the head sums as means over `count` = batch N
 __global__ __launch_bounds__(kThreads) void slab_sum_kernel(const float* ws, size_t stride,
@@ -87,14 +98,15 @@ __global__ __launch_bounds__(kThreads) void slab_sum_kernel(const float* ws, siz
   }
 }
 
-hipError_t launch_then_sum(const void* kernel, const void* params, const TrainParams& p,
-                           int blocks, size_t lds_bytes, hipStream_t stream, int first,
-                           int total) {
-  hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds_bytes);
-  if (err != hipSuccess) return err;
+hipError_t set_dynamic_lds(const void* kernel, size_t lds_bytes) {
+  return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+}
+
+hipError_t launch_prepared_then_sum(const void* kernel, const void* params, const TrainParams& p,
+                                    int blocks, size_t lds_bytes, hipStream_t stream, int first,
+                                    int total) {
   void* args[] = {const_cast<void*>(params)};
-  err = hipLaunchKernel(kernel, dim3(blocks), dim3(kThreads), args, lds_bytes, stream);
+  hipError_t err = hipLaunchKernel(kernel, dim3(blocks), dim3(kThreads), args, lds_bytes, stream);
   if (err != hipSuccess || first >= total) return err;
   const int grid = (total + kThreads - 1) / kThreads;
   hipLaunchKernelGGL(slab_sum_kernel, dim3(grid), dim3(kThreads), 0, stream, p.ws, p.slab_stride,
@@ -103,9 +115,22 @@ hipError_t launch_then_sum(const void* kernel, const void* params, const TrainPa
   return hipGetLastError();
 }
 
+hipError_t launch_then_sum(const void* kernel, const void* params, const TrainParams& p,
+                           int blocks, size_t lds_bytes, hipStream_t stream, int first,
+                           int total) {
+  hipError_t err = set_dynamic_lds(kernel, lds_bytes);
+  if (err != hipSuccess) return err;
+  return launch_prepared_then_sum(kernel, params, p, blocks, lds_bytes, stream, first, total);
+}
+
 hipError_t launch_loss_grad(const TrainParams& p, int blocks, size_t lds_bytes, hipStream_t stream) {
   return launch_then_sum(reinterpret_cast<const void*>(loss_grad_kernel), &p, p, blocks, lds_bytes,
                          stream, p.want_grad ? 0 : p.n_weights, p.n_weights + 2 * p.H);
+}
+
+const void* loss_grad_kernel_entry(bool coef_table) {
+  return coef_table ? reinterpret_cast<const void*>(loss_grad_table_kernel)
+                    : reinterpret_cast<const void*>(loss_grad_kernel);
 }
 
 }  // namespace train

@@ -175,6 +175,21 @@ __device__ __forceinline__ HeadTerms head_terms(float pv, float lv, float bv, fl
   return t;
 }
 
+// head_terms of head h with the loss constants of the call: the host values the kernel
+// arguments carry (floor / coef_abs / coef_rel, TrainParams' or UnrolledParams'), or with
+// kCoefTable the device table p.coef_table [3][heads] that clip_kernel (train_run.hip) wrote.
+// A template flag, not a run-time null: the kernels of the host values compile as before.
+template <bool kCoefTable>
+__device__ __forceinline__ HeadTerms head_terms_of(const TrainParams& p, const float* floor,
+                                                   const float* coef_abs, const float* coef_rel,
+                                                   int heads, int h, float pv, float lv, float bv,
+                                                   float inv_count) {
+  if (kCoefTable)
+    return head_terms(pv, lv, bv, p.coef_table[h], p.coef_table[heads + h],
+                      p.coef_table[2 * heads + h], inv_count);
+  return head_terms(pv, lv, bv, floor[h], coef_abs[h], coef_rel[h], inv_count);
+}
+
 // The LDS rows of one workgroup.  The two [N][H] rows behind gp hold the error terms of
 // the loss until their per-head sums are taken, and the space-derivative cotangents and
 // the state gradient inside evaluation_vjp.

@@ -20,7 +20,9 @@
 namespace ddd {
 namespace train {
 
-__global__ __launch_bounds__(kThreads) void unrolled_loss_grad_kernel(UnrolledParams q) {
+// kCoefTable: the loss constants from q.t.coef_table (head_terms_of, train_device.h)
+template <bool kCoefTable>
+__device__ __forceinline__ void unrolled_loss_grad_body(const UnrolledParams& q) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const TrainParams& p = q.t;
   const int tid = threadIdx.x, n = p.N, H = p.H, D = p.D;
@@ -76,8 +78,9 @@ __global__ __launch_bounds__(kThreads) void unrolled_loss_grad_kernel(UnrolledPa
         for (int i = tid; i < n * H; i += kThreads) {
           const int x = i / H, h = i - x * H;
           const size_t li = loff + (size_t)x * HT + h;
-          const HeadTerms t = head_terms(r.pred[i], p.labels[li], p.baseline[li], q.floor[h],
-                                         q.coef_abs[h], q.coef_rel[h], inv_count);
+          const HeadTerms t = head_terms_of<kCoefTable>(p, q.floor, q.coef_abs, q.coef_rel, HT, h,
+                                                        r.pred[i], p.labels[li], p.baseline[li],
+                                                        inv_count);
           em[i] = t.abs_error;
           er[i] = t.rel_error;
           if (p.predictions != nullptr) p.predictions[poff + (size_t)x * HT + h] = r.pred[i];
@@ -102,8 +105,9 @@ __global__ __launch_bounds__(kThreads) void unrolled_loss_grad_kernel(UnrolledPa
           const float y_new = st[(size_t)(e - 1) * n + x] + dt * r.pred[(size_t)x * H + D];
           if (step + 1 < T) st[(size_t)(e + 1) * n + x] = y_new;
           const size_t li = loff + (size_t)x * HT + h;
-          const HeadTerms t = head_terms(y_new, p.labels[li], p.baseline[li], q.floor[h],
-                                         q.coef_abs[h], q.coef_rel[h], inv_count);
+          const HeadTerms t = head_terms_of<kCoefTable>(p, q.floor, q.coef_abs, q.coef_rel, HT, h,
+                                                        y_new, p.labels[li], p.baseline[li],
+                                                        inv_count);
           r.gdy[x] = t.abs_error;
           r.gfl[x] = t.rel_error;
           gi[(size_t)step * n + x] = t.cotangent;
@@ -128,8 +132,9 @@ __global__ __launch_bounds__(kThreads) void unrolled_loss_grad_kernel(UnrolledPa
           float g = h == D ? c : 0.0f;
           if (e == 0) {
             const size_t li = loff + (size_t)x * HT + h;
-            g += head_terms(r.pred[(size_t)x * H + h], p.labels[li], p.baseline[li], q.floor[h],
-                            q.coef_abs[h], q.coef_rel[h], inv_count).cotangent;
+            g += head_terms_of<kCoefTable>(p, q.floor, q.coef_abs, q.coef_rel, HT, h,
+                                           r.pred[(size_t)x * H + h], p.labels[li],
+                                           p.baseline[li], inv_count).cotangent;
           }
           r.gp[(size_t)x * H + h] = g;
         }
@@ -148,12 +153,25 @@ __global__ __launch_bounds__(kThreads) void unrolled_loss_grad_kernel(UnrolledPa
   }
 }
 
+__global__ __launch_bounds__(kThreads) void unrolled_loss_grad_kernel(UnrolledParams q) {
+  unrolled_loss_grad_body<false>(q);
+}
+
+__global__ __launch_bounds__(kThreads) void unrolled_loss_grad_table_kernel(UnrolledParams q) {
+  unrolled_loss_grad_body<true>(q);
+}
+
 hipError_t launch_unrolled_loss_grad(const UnrolledParams& q, int blocks, size_t lds_bytes,
                                      hipStream_t stream) {
   const TrainParams& p = q.t;
   return launch_then_sum(reinterpret_cast<const void*>(unrolled_loss_grad_kernel), &q, p, blocks,
                          lds_bytes, stream, p.want_grad ? 0 : p.n_weights,
                          p.n_weights + 2 * q.HT);
+}
+
+const void* unrolled_loss_grad_kernel_entry(bool coef_table) {
+  return coef_table ? reinterpret_cast<const void*>(unrolled_loss_grad_table_kernel)
+                    : reinterpret_cast<const void*>(unrolled_loss_grad_kernel);
 }
 
 }  // namespace train

@@ -6,7 +6,9 @@ Reference: training.py:168-189 (set_data_dependent_hparams), 358-417
 (determine_loss_scales), 570-636 (training_loop); model.py:664-810 for the loss.
 The optimiser is torch.optim.Adam(beta2=0.99) on the piecewise-constant schedule
 of learning_rates / learning_stops (training.py:191-218); the gradient comes from
-the kernel, not from autograd.
+the kernel, not from autograd.  Trainer.run / training_loop(fused=True) hand a whole
+stretch of optimiser steps to the device in one call (ddd_train_run, csrc/train_run.hip:
+the same gradient with Adam fused into its slab sum, error_max decided on the device).
 """
 import copy
 import os
@@ -192,6 +194,61 @@ class Trainer(object):
     self.step_count += 1
     return per_head
 
+  def _adam_state(self):
+    """The optimiser's state of the weights (exp_avg, exp_avg_sq, step), created as
+    torch.optim.Adam creates it on its first step."""
+    torch = self.torch
+    state = self.optimizer.state[self.weights]
+    if len(state) == 0:
+      state['step'] = torch.tensor(0.0, dtype=torch.float32)
+      state['exp_avg'] = torch.zeros_like(self.weights, memory_format=torch.preserve_format)
+      state['exp_avg_sq'] = torch.zeros_like(self.weights,
+                                             memory_format=torch.preserve_format)
+    return state
+
+  def run(self, dataset, num_steps: int, sample_index=None) -> np.ndarray:
+    """num_steps optimiser steps in one ddd_train_run call: the gradient of `step`, Adam
+    fused into its slab sum, error_max decided on the device; the host reads once, after
+    the call.  Returns loss_per_head of every step [num_steps, 2, channel], scaled and
+    clipped as `step` returns it.  Minibatches: dataset.batch_indices(), drawn up front,
+    or sample_index, an int32 [num_steps, batch] tensor / array.  Shares the optimiser
+    state with `step`, so the two may be interleaved."""
+    torch = self.torch
+    hp = self.hparams
+    num_steps = int(num_steps)
+    if num_steps < 1:
+      raise ValueError('num_steps = {} (>= 1)'.format(num_steps))
+    if sample_index is None:
+      batches = dataset.batch_indices()
+      rows = [next(batches) for _ in range(num_steps)]
+      sample_index = torch.stack([torch.as_tensor(r, dtype=torch.int32) for r in rows])
+    sample_index = torch.as_tensor(sample_index, dtype=torch.int32).to(
+        self.weights.device).contiguous()
+    if sample_index.dim() != 2 or int(sample_index.shape[0]) != num_steps:
+      raise ValueError('sample_index must be [num_steps, batch]')
+    heads = int(dataset.labels.shape[-1])
+    floor, coef_abs, coef_rel = self.coefficients(heads)
+    scale = np.array(hp.error_scale, np.float64).reshape(2, -1)
+    rates = [learning_rate(hp, self.step_count + k) for k in range(num_steps)]
+    state = self._adam_state()
+    group = self.optimizer.param_groups[0]
+    steps = hp.num_time_steps or 0
+    log, _ = _lib.train_run(
+        self.cfg, self.weights.detach(), state['exp_avg'], state['exp_avg_sq'],
+        dataset.inputs, dataset.labels, dataset.baseline, sample_index, rates, floor,
+        coef_abs, coef_rel, first_step=int(state['step']), betas=group['betas'],
+        epsilon=group['eps'], num_time_steps=steps,
+        time_step=self.model.equation.time_step if steps else 0.0,
+        error_max=hp.error_max or 0.0, error_scale=scale, nullspace=self.nullspace,
+        bias=self.bias)
+    state['step'] += num_steps
+    group['lr'] = rates[-1]
+    self.step_count += num_steps
+    per_head = log.double().cpu().numpy() * scale
+    if hp.error_max:
+      per_head = np.where(per_head < hp.error_max, per_head, hp.error_max)
+    return per_head
+
   def export(self) -> model_lib.LearnedStencilModel:
     """The current weights as a LearnedStencilModel (same equation / hparams)."""
     flat = self.weights.detach().cpu().numpy()
@@ -207,11 +264,14 @@ class Trainer(object):
 
 
 def training_loop(snapshots: np.ndarray, checkpoint_dir: str, hparams,
-                  seed: int = 0, num_steps: int = None) -> List[Dict[str, float]]:
+                  seed: int = 0, num_steps: int = None,
+                  fused: bool = False) -> List[Dict[str, float]]:
   """training.py:570-636: trains on fine snapshots [examples, x], writes hparams.json +
   model.npz (LearnedStencilModel.save) to checkpoint_dir and returns one metrics row
   per eval_interval steps: the validation loss and loss per head.  num_steps defaults
-  to learning_stops[-1]."""
+  to learning_stops[-1].  fused: every stretch between two evaluations is one
+  Trainer.run call (the same minibatch order) instead of eval_interval Trainer.step
+  calls."""
   hparams = copy.deepcopy(hparams)
   _checker(hparams)(hparams)
   train_data = set_data_dependent_hparams(hparams, snapshots, seed)
@@ -234,10 +294,21 @@ def training_loop(snapshots: np.ndarray, checkpoint_dir: str, hparams,
 
   evaluate(0)
   batches = train_data.batch_indices()
-  for step in range(steps):
-    trainer.step(train_data, next(batches))
-    if (step + 1) % hparams.eval_interval == 0:
-      evaluate(step + 1)
+  if fused:
+    torch = trainer.torch
+    step = 0
+    while step < steps:   # up to the next evaluation, or the end
+      stop = min(steps, (step // hparams.eval_interval + 1) * hparams.eval_interval)
+      index = torch.stack([next(batches) for _ in range(stop - step)])
+      trainer.run(train_data, stop - step, index)
+      step = stop
+      if step % hparams.eval_interval == 0:
+        evaluate(step)
+  else:
+    for step in range(steps):
+      trainer.step(train_data, next(batches))
+      if (step + 1) % hparams.eval_interval == 0:
+        evaluate(step + 1)
   trainer.export().save(checkpoint_dir)
   return rows
 

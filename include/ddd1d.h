@@ -547,6 +547,73 @@ DDD_API size_t ddd_train_unrolled_workspace_bytes(const ddd_config* cfg, int bat
 DDD_API int ddd_train_unrolled_loss_grad(const ddd_config* cfg,
                                          const ddd_train_unrolled_args* args, void* stream);
 
+/* ---- the optimiser loop on the device --------------------------------------
+ * Replaces: num_steps iterations of training.training_loop (training.py:570-636)
+ * between two evaluations: per step the loss and gradient of
+ * ddd_train_loss_grad (num_time_steps = 0) or ddd_train_unrolled_loss_grad
+ * (1 <= num_time_steps <= DDD_MAX_TIME_STEPS) on that step's minibatch, then
+ * tf.train.AdamOptimizer's update, which is the single-tensor path of
+ * torch.optim.Adam without weight decay or amsgrad, in float32 and in this order:
+ *   m += (g - m) (1 - beta1);  v = beta2 v + (1 - beta2) g^2;
+ *   denom = sqrt(v) / sqrt(1 - beta2^t) + epsilon;  w -= (lr / (1 - beta1^t)) m / denom
+ * for t = first_step + k + 1 at step k (lr / (1 - beta1^t) and sqrt(1 - beta2^t) are
+ * formed on the host in double).  One call enqueues every step on `stream` and
+ * returns: no stream synchronisation, no copy to the host, no graph capture.  The
+ * update is fused into the kernel that sums the gradient slabs, in their fixed
+ * order, so the gradient of a step is bit for bit what the two entry points above
+ * return for the same weights and minibatch, and equal inputs give equal bits.
+ * error_max > 0 is decided on the device: per step a forward-only pass, then the
+ * coefficient of every term with head_mean * error_scale >= error_max (compared in
+ * double) zeroed for the pass that forms the gradient, as the two-call path of
+ * ddd_train_loss_grad does on the host.  The logged means are the unclipped ones.
+ * H' = num_derivatives + 1 + num_time_steps heads.  Supports exactly the
+ * configurations ddd_train_loss_grad supports and refuses the others with the same
+ * status and text ("training run" as the entry point's name). */
+typedef struct ddd_train_run_args {
+  int32_t struct_size;   /* = sizeof(ddd_train_run_args), checked */
+  int32_t batch;         /* samples per minibatch */
+  int32_t num_rows;      /* S: rows of y / labels / baseline */
+  int32_t num_time_steps; /* T; 0 = the loss of ddd_train_loss_grad */
+  int32_t first_step;    /* optimiser steps already taken (>= 0) */
+  int32_t num_steps;     /* optimiser steps of this call (>= 1) */
+  float* weights;        /* in/out: conv weights (ddd_model_create layout) */
+  float* adam_m;         /* in/out, layout of `weights`: first moment */
+  float* adam_v;         /* in/out, layout of `weights`: second moment */
+  const float* nullspace; /* as ddd_train_args */
+  const float* bias;     /* as ddd_train_args */
+  const float* y;        /* [S][N] coarse inputs */
+  const int32_t* sample_index; /* device [num_steps][batch], required: step k trains
+                                  on rows sample_index[k][0 .. batch-1].  An index
+                                  outside [0, S) makes that step's logged means NaN
+                                  and, through the update, the weights, adam_m and
+                                  adam_v (ddd_train_loss_grad: head_means NaN). */
+  const float* labels;   /* [S][N][H'] */
+  const float* baseline; /* [S][N][H'] */
+  const double* learning_rate; /* HOST [num_steps], finite and >= 0 */
+  double beta1, beta2;   /* in [0, 1) */
+  double epsilon;        /* > 0 */
+  double error_max;      /* 0 = no clipping */
+  double error_scale_abs[DDD_MAX_UNROLLED_HEADS]; /* HOST, first H' used, read with */
+  double error_scale_rel[DDD_MAX_UNROLLED_HEADS]; /* error_max > 0 only            */
+  float error_floor[DDD_MAX_UNROLLED_HEADS]; /* HOST values, first H' used */
+  float coef_abs[DDD_MAX_UNROLLED_HEADS];
+  float coef_rel[DDD_MAX_UNROLLED_HEADS];
+  float time_step;       /* the equation's time_step (T > 0) */
+  float* head_means_log; /* out [num_steps][2][H']: every step's head_means */
+  float* last_grad;      /* out, layout of `weights`, or NULL: the last step's gradient */
+  void* workspace;       /* ddd_train_run_workspace_bytes(cfg, batch, T) bytes */
+  size_t workspace_bytes;
+} ddd_train_run_args;
+
+/* Bytes of the caller-allocated workspace of ddd_train_run: that of
+ * ddd_train_workspace_bytes (T = 0) or ddd_train_unrolled_workspace_bytes plus the
+ * device table of loss constants; depends only on cfg, batch and T.  0 on error. */
+DDD_API size_t ddd_train_run_workspace_bytes(const ddd_config* cfg, int batch,
+                                             int num_time_steps);
+/* Enqueues num_steps optimiser steps.  Arguments are checked before any device work. */
+DDD_API int ddd_train_run(const ddd_config* cfg, const ddd_train_run_args* args,
+                          void* stream);
+
 /* ---- differentiable evaluation --------------------------------------------
  * Replaces: tf.gradients through model.predict_result (model.py:664-697), the
  * building block of the reference's differentiable time integration
