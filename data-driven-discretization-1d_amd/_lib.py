@@ -147,6 +147,47 @@ class DDDTrainRunArgs(ctypes.Structure):
   ]
 
 
+MAX_REPLICAS = 64   # DDD_MAX_REPLICAS
+
+
+class DDDTrainPopulationArgs(ctypes.Structure):
+  """struct ddd_train_population_args."""
+  _fields_ = [
+      ('struct_size', ctypes.c_int32),
+      ('batch', ctypes.c_int32),
+      ('num_rows', ctypes.c_int32),
+      ('num_time_steps', ctypes.c_int32),
+      ('first_step', ctypes.c_int32),
+      ('num_steps', ctypes.c_int32),
+      ('replicas', ctypes.c_int32),
+      ('index_per_replica', ctypes.c_int32),
+      ('weights', ctypes.c_void_p),
+      ('adam_m', ctypes.c_void_p),
+      ('adam_v', ctypes.c_void_p),
+      ('nullspace', ctypes.c_void_p),
+      ('bias', ctypes.c_void_p),
+      ('y', ctypes.c_void_p),
+      ('sample_index', ctypes.c_void_p),
+      ('labels', ctypes.c_void_p),
+      ('baseline', ctypes.c_void_p),
+      ('learning_rate', ctypes.POINTER(ctypes.c_double)),
+      ('beta1', ctypes.c_double),
+      ('beta2', ctypes.c_double),
+      ('epsilon', ctypes.c_double),
+      ('error_max', ctypes.c_double),
+      ('error_scale_abs', ctypes.c_double * MAX_UNROLLED_HEADS),
+      ('error_scale_rel', ctypes.c_double * MAX_UNROLLED_HEADS),
+      ('error_floor', ctypes.c_float * MAX_UNROLLED_HEADS),
+      ('coef_abs', ctypes.c_float * MAX_UNROLLED_HEADS),
+      ('coef_rel', ctypes.c_float * MAX_UNROLLED_HEADS),
+      ('time_step', ctypes.c_float),
+      ('head_means_log', ctypes.c_void_p),
+      ('last_grad', ctypes.c_void_p),
+      ('workspace', ctypes.c_void_p),
+      ('workspace_bytes', ctypes.c_size_t),
+  ]
+
+
 class DDDVjpArgs(ctypes.Structure):
   """struct ddd_vjp_args."""
   _fields_ = [
@@ -260,6 +301,11 @@ SIGNATURES = {
                                                          ctypes.c_int, ctypes.c_int]),
     'ddd_train_run': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
                                      ctypes.POINTER(DDDTrainRunArgs), _V]),
+    'ddd_train_population_workspace_bytes': (ctypes.c_size_t,
+                                             [ctypes.POINTER(DDDConfig), ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int]),
+    'ddd_train_population_run': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
+                                                ctypes.POINTER(DDDTrainPopulationArgs), _V]),
     'ddd_vjp_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(DDDConfig),
                                                    ctypes.c_int]),
     'ddd_result_vjp': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
@@ -632,6 +678,98 @@ def train_run(cfg, weights, adam_m, adam_v, y, labels, baseline, sample_index,
   args.workspace = workspace.data_ptr()
   args.workspace_bytes = workspace.numel()
   check(lib.ddd_train_run(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
+  return log, last_grad
+
+
+def train_population_run(cfg, weights, adam_m, adam_v, y, labels, baseline, sample_index,
+                         learning_rates, error_floor, coef_abs, coef_rel, first_step=0,
+                         betas=(0.9, 0.999), epsilon=1e-8, num_time_steps=0, time_step=0.0,
+                         error_max=0.0, error_scale=None, nullspace=None, bias=None,
+                         want_last_grad=False, workspace=None):
+  """ddd_train_population_run: train_run on R replicas in one call; returns
+  (head_means_log [num_steps, R, 2, H'] device tensor, last_grad [R, n_weights] or None)
+  without waiting for the device.
+
+  weights / adam_m / adam_v are [R, n_weights] (rows in the ddd_model_create layout; a
+  tensor with more rows is taken as its first R), updated in place; learning_rates host
+  floats [R][num_steps]; sample_index an int32 device tensor [num_steps, batch] (one
+  minibatch order for all replicas) or [num_steps, R, batch].  The other arguments, shared
+  by the replicas, as train_run."""
+  lib = load_library()
+  torch = require_gpu()
+  steps = int(num_time_steps)
+  if float(error_max or 0.0) > 0 and error_scale is None:
+    raise ValueError("error_max > 0 needs error_scale [2, H']")
+  rates = [[float(rate) for rate in row] for row in learning_rates]
+  replicas = len(rates)
+  num_steps = len(rates[0]) if rates else 0
+  if any(len(row) != num_steps for row in rates):
+    raise ValueError('learning_rates must be [R][num_steps]')
+  heads = int(labels.shape[-1])
+  if heads != cfg.num_derivatives + 1 + steps:
+    raise ValueError('labels must have num_derivatives + 1 + num_time_steps = {} channels, '
+                     'got {}'.format(cfg.num_derivatives + 1 + steps, heads))
+  if (y.dim() != 2 or tuple(labels.shape) != tuple(y.shape) + (heads,) or
+      tuple(baseline.shape) != tuple(labels.shape) or y.shape[1] != cfg.num_points):
+    raise ValueError("expected y [S, N], labels / baseline [S, N, H']")
+  if (not isinstance(sample_index, torch.Tensor) or sample_index.dtype != torch.int32 or
+      not sample_index.is_cuda or not sample_index.is_contiguous() or
+      sample_index.dim() not in (2, 3) or int(sample_index.shape[0]) != num_steps or
+      (sample_index.dim() == 3 and int(sample_index.shape[1]) != replicas)):
+    raise ValueError('sample_index must be a contiguous int32 device tensor '
+                     '[num_steps, batch] or [num_steps, R, batch]')
+  batch = int(sample_index.shape[-1])
+  ws_bytes = lib.ddd_train_population_workspace_bytes(ctypes.byref(cfg), batch, steps, replicas)
+  if ws_bytes == 0:
+    check(-1)
+  n_weights = vjp_num_weights(cfg)
+  for name, tensor in (('weights', weights), ('adam_m', adam_m), ('adam_v', adam_v)):
+    rows = int(tensor.shape[0]) if isinstance(tensor, torch.Tensor) and tensor.dim() == 2 else 0
+    if rows < replicas:
+      raise ValueError('{} must be [R, n_weights] with R = {} rows'.format(name, replicas))
+    _check_f32_device(name, tensor, (rows, n_weights))
+  for name, tensor in (('y', y), ('labels', labels), ('baseline', baseline),
+                       ('nullspace', nullspace), ('bias', bias)):
+    if tensor is not None:
+      _check_f32_device(name, tensor, tuple(tensor.shape))
+  if workspace is None or workspace.numel() < ws_bytes:
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
+  log = torch.empty((num_steps, replicas, 2, heads), dtype=torch.float32, device=y.device)
+  last_grad = (torch.empty((replicas, n_weights), dtype=torch.float32, device=y.device)
+               if want_last_grad else None)
+  args = DDDTrainPopulationArgs()
+  args.struct_size = ctypes.sizeof(DDDTrainPopulationArgs)
+  args.batch = batch
+  args.num_rows = int(y.shape[0])
+  args.num_time_steps = steps
+  args.first_step = int(first_step)
+  args.num_steps = num_steps
+  args.replicas = replicas
+  args.index_per_replica = 1 if sample_index.dim() == 3 else 0
+  for name, tensor in (('weights', weights), ('adam_m', adam_m), ('adam_v', adam_v),
+                       ('y', y), ('labels', labels), ('baseline', baseline),
+                       ('sample_index', sample_index), ('head_means_log', log)):
+    setattr(args, name, tensor.data_ptr())
+  args.nullspace = None if nullspace is None else nullspace.data_ptr()
+  args.bias = None if bias is None else bias.data_ptr()
+  flat = [rate for row in rates for rate in row]
+  rate_array = (ctypes.c_double * max(len(flat), 1))(*flat)
+  args.learning_rate = ctypes.cast(rate_array, ctypes.POINTER(ctypes.c_double))
+  args.beta1, args.beta2 = float(betas[0]), float(betas[1])
+  args.epsilon = float(epsilon)
+  args.error_max = float(error_max or 0.0)
+  for h in range(heads):
+    args.error_floor[h] = float(error_floor[h])
+    args.coef_abs[h] = float(coef_abs[h])
+    args.coef_rel[h] = float(coef_rel[h])
+    if error_scale is not None:
+      args.error_scale_abs[h] = float(error_scale[0][h])
+      args.error_scale_rel[h] = float(error_scale[1][h])
+  args.time_step = float(time_step)
+  args.last_grad = None if last_grad is None else last_grad.data_ptr()
+  args.workspace = workspace.data_ptr()
+  args.workspace_bytes = workspace.numel()
+  check(lib.ddd_train_population_run(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
   return log, last_grad
 
 

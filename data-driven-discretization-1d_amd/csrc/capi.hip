@@ -35,6 +35,7 @@
 #include "rhs_stream.h"
 #include "ring_args.h"
 #include "train.h"
+#include "train_population.h"
 #include "train_run.h"
 #include "train_unrolled.h"
 #include "rhs_weno.h"   // (host side only: weno::supports; the kernels are weno_unit.hip)
@@ -1486,10 +1487,11 @@ int train_unrolled_params(const ddd_config* cfg, int batch, int num_time_steps,
 
 // The configuration checks and kernel parameters of ddd_train_run (train_run.h):
 // train_params into r->q.t for num_time_steps = 0 (r->q.T = 0), train_unrolled_params
-// otherwise, named "training run"; the workspace is theirs plus the coefficient table.
+// otherwise, named "training run" (ddd_train_population_run: "training population"); the
+// workspace is theirs plus the coefficient table.
 int train_run_params(const ddd_config* cfg, int batch, int num_time_steps,
-                     ddd::train::RunParams* r, size_t* ws_bytes) {
-  static const char* who = "training run";
+                     ddd::train::RunParams* r, size_t* ws_bytes,
+                     const char* who = "training run") {
   std::memset(r, 0, sizeof(*r));
   size_t slabs = 0;
   int rc;
@@ -1505,6 +1507,113 @@ int train_run_params(const ddd_config* cfg, int batch, int num_time_steps,
   if (rc) return rc;
   r->heads = r->q.HT;
   *ws_bytes = slabs + ddd::train::kCoefTableBytes;   // (slabs: a multiple of 16 bytes)
+  return DDD_OK;
+}
+
+static_assert(ddd::train::kMaxReplicas == DDD_MAX_REPLICAS, "train_population.h / ddd1d.h");
+
+// train_run_params under the name "training population", then the replica count: *ws_bytes
+// is the workspace of ONE replica (ddd_train_run_workspace_bytes)
+int train_population_params(const ddd_config* cfg, int batch, int num_time_steps, int replicas,
+                            ddd::train::RunParams* r, size_t* ws_bytes) {
+  int rc = train_run_params(cfg, batch, num_time_steps, r, ws_bytes, "training population");
+  if (rc) return rc;
+  if (replicas < 1 || replicas > DDD_MAX_REPLICAS)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "replicas = %d out of range [1, %d]", replicas,
+                DDD_MAX_REPLICAS);
+  return DDD_OK;
+}
+
+// What ddd_train_run and ddd_train_population_run check and copy alike, for Args =
+// ddd_train_run_args / ddd_train_population_args (equally named fields): the arguments
+// into r, whose configuration train_run_params has filled.  ws: the bytes the workspace
+// must have, named ws_bytes_fn in the message; the coefficient table(s) lie table_offset
+// bytes into it.  replicas: 0 for ddd_train_run (learning_rate [num_steps]), otherwise
+// R (learning_rate [R][num_steps]).
+template <typename Args>
+int train_run_args(const Args* a, ddd::train::RunParams& r, size_t ws, size_t table_offset,
+                   int replicas, const char* ws_bytes_fn) {
+  ddd::train::TrainParams& p = r.q.t;
+  if (!a->weights || !a->adam_m || !a->adam_v || !a->y || !a->labels || !a->baseline ||
+      !a->sample_index || !a->learning_rate || !a->head_means_log)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "weights, adam_m, adam_v, y, labels, baseline, sample_index, learning_rate "
+                "and head_means_log must not be NULL");
+  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
+  if (projected && (!a->nullspace || !a->bias))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "nullspace/bias required for model_target 'coefficients' with "
+                "polynomial_accuracy_order > 0");
+  if (a->num_rows < 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
+  if (a->num_steps < 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_steps = %d (>= 1)", a->num_steps);
+  if (a->first_step < 0)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "first_step = %d (>= 0)", a->first_step);
+  for (int i = 0; i < std::max(replicas, 1); ++i)
+    for (int k = 0; k < a->num_steps; ++k) {
+      const double rate = a->learning_rate[(size_t)i * a->num_steps + k];
+      if (std::isfinite(rate) && rate >= 0.0) continue;
+      if (replicas == 0)
+        return fail(DDD_ERR_INVALID_ARGUMENT, "learning_rate of step %d is %g (finite, >= 0)",
+                    k, rate);
+      return fail(DDD_ERR_INVALID_ARGUMENT,
+                  "learning_rate of replica %d, step %d is %g (finite, >= 0)", i, k, rate);
+    }
+  if (!(a->beta1 >= 0.0 && a->beta1 < 1.0) || !(a->beta2 >= 0.0 && a->beta2 < 1.0))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "beta1 = %g, beta2 = %g outside [0, 1)", a->beta1,
+                a->beta2);
+  if (!(a->epsilon > 0.0) || !std::isfinite(a->epsilon))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "epsilon = %g (> 0)", a->epsilon);
+  if (!(a->error_max >= 0.0) || !std::isfinite(a->error_max))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "error_max = %g (>= 0)", a->error_max);
+  if (a->num_time_steps > 0 && !std::isfinite(a->time_step))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
+  if (a->workspace == nullptr || a->workspace_bytes < ws)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "workspace of %zu bytes given, %s = %zu",
+                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws_bytes_fn, ws);
+  for (int h = 0; h < r.heads; ++h) {
+    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
+        !std::isfinite(a->coef_rel[h]))
+      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
+    if (a->error_max > 0.0 &&
+        (!std::isfinite(a->error_scale_abs[h]) || !std::isfinite(a->error_scale_rel[h])))
+      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_scale of head %d", h);
+    r.floor[h] = r.q.floor[h] = a->error_floor[h];
+    r.coef_abs[h] = r.q.coef_abs[h] = a->coef_abs[h];
+    r.coef_rel[h] = r.q.coef_rel[h] = a->coef_rel[h];
+    if (r.q.T == 0) {   // (heads = H <= kMaxHeads)
+      p.floor[h] = a->error_floor[h];
+      p.coef_abs[h] = a->coef_abs[h];
+      p.coef_rel[h] = a->coef_rel[h];
+    }
+    r.scale_abs[h] = a->error_scale_abs[h];
+    r.scale_rel[h] = a->error_scale_rel[h];
+  }
+  p.weights = a->weights;
+  p.nullspace = projected ? a->nullspace : nullptr;
+  p.bias = projected ? a->bias : nullptr;
+  p.y = a->y;
+  p.rows = a->num_rows;
+  p.labels = a->labels;
+  p.baseline = a->baseline;
+  p.predictions = nullptr;
+  p.ws = static_cast<float*>(a->workspace);
+  r.q.dt = a->time_step;
+  r.first_step = a->first_step;
+  r.num_steps = a->num_steps;
+  r.learning_rate = a->learning_rate;
+  r.beta1 = a->beta1;
+  r.beta2 = a->beta2;
+  r.epsilon = a->epsilon;
+  r.sample_index = a->sample_index;
+  r.weights = a->weights;
+  r.adam_m = a->adam_m;
+  r.adam_v = a->adam_v;
+  r.head_means_log = a->head_means_log;
+  r.last_grad = a->last_grad;
+  r.error_max = a->error_max;
+  r.coef_table = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + table_offset);
   return DDD_OK;
 }
 
@@ -2647,84 +2756,43 @@ int ddd_train_run(const ddd_config* cfg, const ddd_train_run_args* a, void* stre
   size_t ws = 0;
   int rc = train_run_params(cfg, a->batch, a->num_time_steps, &r, &ws);
   if (rc) return rc;
-  ddd::train::TrainParams& p = r.q.t;
-  if (!a->weights || !a->adam_m || !a->adam_v || !a->y || !a->labels || !a->baseline ||
-      !a->sample_index || !a->learning_rate || !a->head_means_log)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "weights, adam_m, adam_v, y, labels, baseline, sample_index, learning_rate "
-                "and head_means_log must not be NULL");
-  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
-  if (projected && (!a->nullspace || !a->bias))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "nullspace/bias required for model_target 'coefficients' with "
-                "polynomial_accuracy_order > 0");
-  if (a->num_rows < 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
-  if (a->num_steps < 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "num_steps = %d (>= 1)", a->num_steps);
-  if (a->first_step < 0)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "first_step = %d (>= 0)", a->first_step);
-  for (int k = 0; k < a->num_steps; ++k)
-    if (!std::isfinite(a->learning_rate[k]) || a->learning_rate[k] < 0.0)
-      return fail(DDD_ERR_INVALID_ARGUMENT, "learning_rate of step %d is %g (finite, >= 0)",
-                  k, a->learning_rate[k]);
-  if (!(a->beta1 >= 0.0 && a->beta1 < 1.0) || !(a->beta2 >= 0.0 && a->beta2 < 1.0))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "beta1 = %g, beta2 = %g outside [0, 1)", a->beta1,
-                a->beta2);
-  if (!(a->epsilon > 0.0) || !std::isfinite(a->epsilon))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "epsilon = %g (> 0)", a->epsilon);
-  if (!(a->error_max >= 0.0) || !std::isfinite(a->error_max))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "error_max = %g (>= 0)", a->error_max);
-  if (a->num_time_steps > 0 && !std::isfinite(a->time_step))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
-  if (a->workspace == nullptr || a->workspace_bytes < ws)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "workspace of %zu bytes given, ddd_train_run_workspace_bytes = %zu",
-                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws);
-  for (int h = 0; h < r.heads; ++h) {
-    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
-        !std::isfinite(a->coef_rel[h]))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
-    if (a->error_max > 0.0 &&
-        (!std::isfinite(a->error_scale_abs[h]) || !std::isfinite(a->error_scale_rel[h])))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_scale of head %d", h);
-    r.floor[h] = r.q.floor[h] = a->error_floor[h];
-    r.coef_abs[h] = r.q.coef_abs[h] = a->coef_abs[h];
-    r.coef_rel[h] = r.q.coef_rel[h] = a->coef_rel[h];
-    if (r.q.T == 0) {   // (heads = H <= kMaxHeads)
-      p.floor[h] = a->error_floor[h];
-      p.coef_abs[h] = a->coef_abs[h];
-      p.coef_rel[h] = a->coef_rel[h];
-    }
-    r.scale_abs[h] = a->error_scale_abs[h];
-    r.scale_rel[h] = a->error_scale_rel[h];
-  }
-  p.weights = a->weights;
-  p.nullspace = projected ? a->nullspace : nullptr;
-  p.bias = projected ? a->bias : nullptr;
-  p.y = a->y;
-  p.rows = a->num_rows;
-  p.labels = a->labels;
-  p.baseline = a->baseline;
-  p.predictions = nullptr;
-  p.ws = static_cast<float*>(a->workspace);
-  r.q.dt = a->time_step;
-  r.first_step = a->first_step;
-  r.num_steps = a->num_steps;
-  r.learning_rate = a->learning_rate;
-  r.beta1 = a->beta1;
-  r.beta2 = a->beta2;
-  r.epsilon = a->epsilon;
-  r.sample_index = a->sample_index;
-  r.weights = a->weights;
-  r.adam_m = a->adam_m;
-  r.adam_v = a->adam_v;
-  r.head_means_log = a->head_means_log;
-  r.last_grad = a->last_grad;
-  r.error_max = a->error_max;
-  r.coef_table = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + ws -
-                                          ddd::train::kCoefTableBytes);
+  rc = train_run_args(a, r, ws, ws - ddd::train::kCoefTableBytes, 0,
+                      "ddd_train_run_workspace_bytes");
+  if (rc) return rc;
   DDD_HIP(ddd::train::launch_train_run(r, static_cast<hipStream_t>(stream)));
+  return DDD_OK;
+}
+
+size_t ddd_train_population_workspace_bytes(const ddd_config* cfg, int batch, int num_time_steps,
+                                            int replicas) {
+  ddd::train::RunParams r;
+  size_t ws = 0;
+  if (train_population_params(cfg, batch, num_time_steps, replicas, &r, &ws)) return 0;
+  return (size_t)replicas * ws;
+}
+
+int ddd_train_population_run(const ddd_config* cfg, const ddd_train_population_args* a,
+                             void* stream) {
+  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
+  if (a->struct_size != (int32_t)sizeof(ddd_train_population_args))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_train_population_args.struct_size = %d, library expects %d (ABI mismatch)",
+                a->struct_size, (int)sizeof(ddd_train_population_args));
+  ddd::train::PopulationParams pp;
+  size_t ws = 0;
+  int rc = train_population_params(cfg, a->batch, a->num_time_steps, a->replicas, &pp.r, &ws);
+  if (rc) return rc;
+  if (a->index_per_replica != 0 && a->index_per_replica != 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "index_per_replica = %d (0 or 1)",
+                a->index_per_replica);
+  // the R replicas' slabs, then their R coefficient tables
+  const size_t slabs = ws - ddd::train::kCoefTableBytes;
+  rc = train_run_args(a, pp.r, (size_t)a->replicas * ws, (size_t)a->replicas * slabs,
+                      a->replicas, "ddd_train_population_workspace_bytes");
+  if (rc) return rc;
+  pp.replicas = a->replicas;
+  pp.index_per_replica = a->index_per_replica;
+  DDD_HIP(ddd::train::launch_train_population(pp, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }
 

@@ -23,6 +23,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "dev_params.h"
 
 namespace ddd {
@@ -57,11 +59,17 @@ struct TrainParams {
   float* predictions;      // [batch][N][H] or null
   float* ws;               // [blocks][slab_stride]
   int want_grad;
+  int index_stride;        // entries between two replicas' rows of sample_index (population
+                           // kernels, train_population.h: batch or 0); elsewhere not read
   float* grad;             // [n_weights] or null
   float* head_means;       // [2][H]
   const float* coef_table; // device [3][heads]: floor, coef_abs, coef_rel, read instead of the
                            // host values by the kernels built for it (train_run.h), or null
 };
+
+static_assert(offsetof(TrainParams, grad) == offsetof(TrainParams, index_stride) + 4 &&
+                  offsetof(TrainParams, index_stride) == offsetof(TrainParams, want_grad) + 4,
+              "index_stride fills the padding behind want_grad");
 
 // The LDS plan of a workgroup (train_device.h: Rows): rows of [N] (the state, the
 // time-derivative cotangent, the flux), of [N][H] (predictions, their cotangent, the two

@@ -57,12 +57,22 @@ __device__ __forceinline__ float rhs_state_partial(int eq, const float (&dv)[kMa
   }
 }
 
+// The kernels of train_population.hip run R replicas on a grid (blocks, R): workgroup
+// (b, r) is workgroup b of replica r, whose weights, slabs, minibatch and coefficient
+// table lie r strides behind replica 0's (the pointers of p).  kReplicas is a template
+// flag, false by default: every other kernel is one replica and compiles as before.
+template <bool kReplicas>
+__device__ __forceinline__ const float* weights_of(const TrainParams& p) {
+  return kReplicas ? p.weights + (size_t)blockIdx.y * p.n_weights : p.weights;
+}
+
 // out[x][co] = bias[co] + sum_k sum_ci in[x + k - K/2][ci] w[k][ci][co]  (periodic), the
 // pre-activation also stored to `z` (global) when non-null, out = act(pre-activation)
+template <bool kReplicas = false>
 __device__ inline void conv_forward(const TrainParams& p, int l, const float* in, float* out,
                                     float* z, int act) {
   const int n = p.N, cin = p.cin[l], cout = p.cout[l], left = p.K / 2;
-  const float* __restrict__ w = p.weights + p.w_off[l];
+  const float* __restrict__ w = weights_of<kReplicas>(p) + p.w_off[l];
   const float* __restrict__ b = w + (size_t)p.K * cin * cout;
   for (int idx = threadIdx.x; idx < n * cout; idx += kThreads) {
     const int x = idx / cout, co = idx - x * cout;
@@ -87,12 +97,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ int mfma_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // conv_forward for a staged layer: in [N][32] -> out / z [N][32]
+template <bool kReplicas = false>
 __device__ inline void conv_forward_mfma(const TrainParams& p, int l, const float* wl,
                                          const float* in, float* out, float* z, int act) {
   const int n = p.N, left = p.K / 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, half = lane >> 5;
   const float* __restrict__ w = wl + p.wl_off[l];
-  const float* __restrict__ b = p.weights + p.w_off[l] + (size_t)p.K * 32 * 32;
+  const float* __restrict__ b = weights_of<kReplicas>(p) + p.w_off[l] + (size_t)p.K * 32 * 32;
   for (int t = wave; t < n / 32; t += kThreads / 64) {
     const int x0 = 32 * t;
     f32x16 acc;
@@ -179,14 +190,16 @@ __device__ __forceinline__ HeadTerms head_terms(float pv, float lv, float bv, fl
 // arguments carry (floor / coef_abs / coef_rel, TrainParams' or UnrolledParams'), or with
 // kCoefTable the device table p.coef_table [3][heads] that clip_kernel (train_run.hip) wrote.
 // A template flag, not a run-time null: the kernels of the host values compile as before.
-template <bool kCoefTable>
+template <bool kCoefTable, bool kReplicas = false>
 __device__ __forceinline__ HeadTerms head_terms_of(const TrainParams& p, const float* floor,
                                                    const float* coef_abs, const float* coef_rel,
                                                    int heads, int h, float pv, float lv, float bv,
                                                    float inv_count) {
-  if (kCoefTable)
-    return head_terms(pv, lv, bv, p.coef_table[h], p.coef_table[heads + h],
-                      p.coef_table[2 * heads + h], inv_count);
+  if (kCoefTable) {
+    const float* table =
+        kReplicas ? p.coef_table + (size_t)blockIdx.y * (3 * heads) : p.coef_table;
+    return head_terms(pv, lv, bv, table[h], table[heads + h], table[2 * heads + h], inv_count);
+  }
   return head_terms(pv, lv, bv, floor[h], coef_abs[h], coef_rel[h], inv_count);
 }
 
@@ -234,13 +247,14 @@ __device__ __forceinline__ Rows carve_rows(const TrainParams& p, float* smem, bo
 
 // A workgroup's prologue: the first n_zero floats of its slab cleared (the sums it adds
 // into), the 32 x 32 kernels of the MFMA layers copied into wl.  Block-wide.
+template <bool kReplicas = false>
 __device__ __forceinline__ void stage_workgroup(const TrainParams& p, float* slab, int n_zero,
                                                 float* wl) {
   const int tid = threadIdx.x;
   for (int i = tid; i < n_zero; i += kThreads) slab[i] = 0.0f;
   for (int l = 0; l < p.L; ++l) {
     if (p.wl_off[l] < 0) continue;
-    const float* src = p.weights + p.w_off[l];
+    const float* src = weights_of<kReplicas>(p) + p.w_off[l];
     for (int i = tid; i < p.K * 32 * 32; i += kThreads) wl[p.wl_off[l] + i] = src[i];
   }
   __syncthreads();
@@ -251,6 +265,7 @@ __device__ __forceinline__ void stage_workgroup(const TrainParams& p, float* sla
 // hidden layers' pre-activations to zs, then the stencils and the equation of motion
 // into pred [N][H] (the flux / right-hand side passes through gfl).  On return *cur
 // holds the net output [N][C_out].  Block-wide: every thread calls it.
+template <bool kReplicas = false>
 __device__ __forceinline__ void forward_sample(const TrainParams& p, const float* wl, float* zs,
                                                const float* u, float* gfl, float* pred,
                                                float*& cur, float*& nxt) {
@@ -261,10 +276,11 @@ __device__ __forceinline__ void forward_sample(const TrainParams& p, const float
   for (int l = 0; l < p.L; ++l) {
     const bool last = l == p.L - 1;
     if (p.wl_off[l] >= 0)
-      conv_forward_mfma(p, l, wl, cur, nxt, last ? nullptr : zs + p.z_off[l],
-                        last ? ACT_NONE : p.act);
+      conv_forward_mfma<kReplicas>(p, l, wl, cur, nxt, last ? nullptr : zs + p.z_off[l],
+                                   last ? ACT_NONE : p.act);
     else
-      conv_forward(p, l, cur, nxt, last ? nullptr : zs + p.z_off[l], last ? ACT_NONE : p.act);
+      conv_forward<kReplicas>(p, l, cur, nxt, last ? nullptr : zs + p.z_off[l],
+                              last ? ACT_NONE : p.act);
     __syncthreads();
     float* t = cur; cur = nxt; nxt = t;
   }
@@ -322,6 +338,7 @@ __device__ __forceinline__ void forward_sample(const TrainParams& p, const float
 // below over act_in.  With grad_y non-null, layer 0's transposed convolution down to its
 // single input channel, times 1 / stddev, plus the LDS row gu, goes to grad_y [N] (the
 // state gradient through the tower's input).  gz and act_in are overwritten.
+template <bool kReplicas = false>
 __device__ __forceinline__ void tower_backward(const TrainParams& p, const float* wl,
                                                const float* zs, const float* u, float* gz,
                                                float* act_in, float* gw_base, bool want_w,
@@ -361,7 +378,8 @@ __device__ __forceinline__ void tower_backward(const TrainParams& p, const float
           float acc = 0.0f;
           for (int k = 0; k < p.K; ++k) {
             const float* __restrict__ g = gz + (size_t)wrap(y - k + left, n) * cout;
-            const float* __restrict__ wk = p.weights + p.w_off[0] + (size_t)k * cout;
+            const float* __restrict__ wk =
+                weights_of<kReplicas>(p) + p.w_off[0] + (size_t)k * cout;
             for (int co = 0; co < cout; ++co) acc = fmaf(g[co], wk[co], acc);
           }
           grad_y[y] = gu[y] + acc / p.stddev;
@@ -370,7 +388,7 @@ __device__ __forceinline__ void tower_backward(const TrainParams& p, const float
     }
     __syncthreads();
     // d loss / d pre-activation of layer l - 1 (transposed convolution), over act_in
-    const float* __restrict__ w = p.weights + p.w_off[l];
+    const float* __restrict__ w = weights_of<kReplicas>(p) + p.w_off[l];
     const float* z = zs + p.z_off[l - 1];
     if (p.wl_off[l] >= 0) conv_backward_data_mfma(p, l, wl, gz, z, act_in);
     else
@@ -404,7 +422,7 @@ __device__ __forceinline__ void tower_backward(const TrainParams& p, const float
 // r.gsd and r.gu are overwritten, the last two behind two barriers.  kStateGrad false
 // (training: grad_y is null in every call) leaves gs and the state gradient unformed.
 // Block-wide.
-template <bool kStateGrad>
+template <bool kStateGrad, bool kReplicas = false>
 __device__ __forceinline__ void evaluation_vjp(const TrainParams& p, const Rows& r,
                                                const float* zs, float* cur, float* nxt,
                                                float* slab, bool want_w, float* grad_y) {
@@ -491,7 +509,8 @@ __device__ __forceinline__ void evaluation_vjp(const TrainParams& p, const Rows&
   }
   // ---- the tower, top down (the net output is no longer needed); term (c) and the
   // state gradient's store at layer 0
-  tower_backward(p, r.wl, zs, u, gz, cur, slab, want_w, r.gu, kStateGrad ? grad_y : nullptr);
+  tower_backward<kReplicas>(p, r.wl, zs, u, gz, cur, slab, want_w, r.gu,
+                            kStateGrad ? grad_y : nullptr);
   __syncthreads();
 }
 

@@ -9,6 +9,9 @@ of learning_rates / learning_stops (training.py:191-218); the gradient comes fro
 the kernel, not from autograd.  Trainer.run / training_loop(fused=True) hand a whole
 stretch of optimiser steps to the device in one call (ddd_train_run, csrc/train_run.hip:
 the same gradient with Adam fused into its slab sum, error_max decided on the device).
+PopulationTrainer / training_population train R replicas of one architecture -- R initial
+seeds, R learning-rate schedules -- in one such call (ddd_train_population_run,
+csrc/train_population.hip): the replicas are a second grid dimension of the same kernels.
 """
 import copy
 import os
@@ -261,6 +264,170 @@ class Trainer(object):
     return model_lib.LearnedStencilModel(
         self.model.equation, self.hparams, kernels, biases, self.model.nullspaces,
         self.model.biases)
+
+
+class PopulationTrainer(object):
+  """R replicas of one architecture on one equation, trained together
+  (ddd_train_population_run, csrc/train_population.hip): `weights` is one [R, n_weights]
+  device tensor, Adam's state (`adam_m`, `adam_v`, beta2 = 0.99 as Trainer) [R, n_weights],
+  one step count for all.  learning_rates[r], when given, replaces hparams.learning_rates
+  for replica r on the same learning_stops.  Replica r of `run` is bit for bit
+  Trainer.run on models[r] with that schedule."""
+
+  BETAS = (0.9, 0.99)
+  EPSILON = 1e-8   # torch.optim.Adam's default, Trainer's
+
+  def __init__(self, models: Sequence[model_lib.LearnedStencilModel], hparams,
+               learning_rates=None):
+    models = list(models)
+    if not 1 <= len(models) <= _lib.MAX_REPLICAS:
+      raise ValueError('{} models (1 .. {})'.format(len(models), _lib.MAX_REPLICAS))
+    _checker(hparams)(hparams)
+    configs = [bytes(_train_config(model)) for model in models]
+    for r, model in enumerate(models):
+      if type(model.equation) is not type(models[0].equation):
+        raise ValueError('replica {} solves {}, replica 0 {}: one equation per '
+                         'population'.format(r, type(model.equation).__name__,
+                                             type(models[0].equation).__name__))
+      if (configs[r] != configs[0] or [w.shape for w in model.conv_kernels] !=
+          [w.shape for w in models[0].conv_kernels]):
+        raise ValueError('replica {} differs from replica 0 in its architecture or grid: '
+                         'one architecture per population'.format(r))
+    if learning_rates is not None:
+      learning_rates = [[float(rate) for rate in row] for row in learning_rates]
+      if len(learning_rates) != len(models):
+        raise ValueError('learning_rates must have one row per replica')
+      if any(len(row) != len(hparams.learning_rates) for row in learning_rates):
+        raise ValueError('every row of learning_rates must have len(hparams.learning_rates) '
+                         '= {} entries'.format(len(hparams.learning_rates)))
+    import torch
+    self.torch = torch
+    self.models = models
+    self.hparams = hparams
+    self.replica_hparams = []
+    for r in range(len(models)):
+      hp = copy.copy(hparams)
+      if learning_rates is not None:
+        hp.learning_rates = learning_rates[r]
+      self.replica_hparams.append(hp)
+    # one Trainer per replica for what needs no population call (the forward-only loss,
+    # export), each on its row of `weights`
+    self.trainers = [Trainer(model, hparams) for model in models]
+    self.cfg = self.trainers[0].cfg
+    self.nullspace, self.bias = self.trainers[0].nullspace, self.trainers[0].bias
+    self.weights = torch.stack([t.weights.detach() for t in self.trainers]).contiguous()
+    for r, trainer in enumerate(self.trainers):
+      trainer.weights = self.weights[r]
+      trainer.optimizer = None   # (the state is this object's)
+    self.adam_m = torch.zeros_like(self.weights)
+    self.adam_v = torch.zeros_like(self.weights)
+    self.step_count = 0
+
+  @property
+  def replicas(self) -> int:
+    return len(self.models)
+
+  def learning_rate_table(self, num_steps: int) -> List[List[float]]:
+    """[R][num_steps]: replica r's learning rate at steps step_count .. + num_steps - 1."""
+    return [[learning_rate(hp, self.step_count + k) for k in range(num_steps)]
+            for hp in self.replica_hparams]
+
+  def run(self, dataset, num_steps: int, sample_index=None) -> np.ndarray:
+    """num_steps optimiser steps of every replica in one call.  Returns loss_per_head
+    [num_steps, R, 2, channel], scaled and clipped as Trainer.run returns it.
+    Minibatches: dataset.batch_indices(), drawn up front and shared, or sample_index,
+    int32 [num_steps, batch] (shared) or [num_steps, R, batch]."""
+    torch = self.torch
+    hp = self.hparams
+    num_steps = int(num_steps)
+    if num_steps < 1:
+      raise ValueError('num_steps = {} (>= 1)'.format(num_steps))
+    if sample_index is None:
+      batches = dataset.batch_indices()
+      rows = [next(batches) for _ in range(num_steps)]
+      sample_index = torch.stack([torch.as_tensor(r, dtype=torch.int32) for r in rows])
+    sample_index = torch.as_tensor(sample_index, dtype=torch.int32).to(
+        self.weights.device).contiguous()
+    if (sample_index.dim() not in (2, 3) or int(sample_index.shape[0]) != num_steps or
+        (sample_index.dim() == 3 and int(sample_index.shape[1]) != self.replicas)):
+      raise ValueError('sample_index must be [num_steps, batch] or [num_steps, R, batch]')
+    heads = int(dataset.labels.shape[-1])
+    floor, coef_abs, coef_rel = self.trainers[0].coefficients(heads)
+    scale = np.array(hp.error_scale, np.float64).reshape(2, -1)
+    steps = hp.num_time_steps or 0
+    log, _ = _lib.train_population_run(
+        self.cfg, self.weights, self.adam_m, self.adam_v, dataset.inputs, dataset.labels,
+        dataset.baseline, sample_index, self.learning_rate_table(num_steps), floor, coef_abs,
+        coef_rel, first_step=self.step_count, betas=self.BETAS, epsilon=self.EPSILON,
+        num_time_steps=steps,
+        time_step=self.models[0].equation.time_step if steps else 0.0,
+        error_max=hp.error_max or 0.0, error_scale=scale, nullspace=self.nullspace,
+        bias=self.bias)
+    self.step_count += num_steps
+    per_head = log.double().cpu().numpy() * scale
+    if hp.error_max:
+      per_head = np.where(per_head < hp.error_max, per_head, hp.error_max)
+    return per_head
+
+  def loss(self, dataset) -> np.ndarray:
+    """loss_per_head [R, 2, channel] over the whole dataset, forward only (one
+    ddd_train_loss_grad / ddd_train_unrolled_loss_grad call per replica)."""
+    return np.stack([trainer.loss_and_grad(dataset, want_grad=False)[0]
+                     for trainer in self.trainers])
+
+  def export(self) -> List[model_lib.LearnedStencilModel]:
+    """The current weights as R LearnedStencilModels."""
+    return [trainer.export() for trainer in self.trainers]
+
+
+def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], hparams,
+                        init_seeds: Sequence[int], learning_rates=None, seed: int = 0,
+                        num_steps: int = None) -> List[List[Dict[str, float]]]:
+  """training_loop(..., seed=seed, fused=True) for R replicas at once: the same dataset,
+  train / validation split and minibatch order; replica r starts from
+  LearnedStencilModel(coarse, hparams, init_seed=init_seeds[r]) and follows
+  learning_rates[r] (default: hparams.learning_rates); every stretch between two
+  evaluations is one PopulationTrainer.run.  Writes hparams.json + model.npz to
+  checkpoint_dirs[r]; returns one list of metric rows per replica."""
+  if len(checkpoint_dirs) != len(init_seeds):
+    raise ValueError('one checkpoint directory per init seed')
+  hparams = copy.deepcopy(hparams)
+  _checker(hparams)(hparams)
+  train_data = set_data_dependent_hparams(hparams, snapshots, seed)
+  train_data.repeat = True
+  valid_data = model_lib.make_dataset(snapshots, hparams, model_lib.Dataset.VALIDATION,
+                                      repeat=False, evaluation=True, seed=seed)
+  for checkpoint_dir in checkpoint_dirs:
+    os.makedirs(checkpoint_dir, exist_ok=True)
+    hparams_lib.save_hparams(hparams, checkpoint_dir)
+  _, coarse = equations_lib.from_hparams(hparams, random_seed=seed)
+  trainer = PopulationTrainer(
+      [model_lib.LearnedStencilModel(coarse, hparams, init_seed=int(s)) for s in init_seeds],
+      hparams, learning_rates)
+  steps = hparams.learning_stops[-1] if num_steps is None else int(num_steps)
+  weights = model_lib.loss_weights(hparams, int(train_data.labels.shape[-1]))
+  rows = [[] for _ in init_seeds]
+
+  def evaluate(step):
+    data = valid_data if valid_data.num_examples else train_data
+    for replica_rows, per_head in zip(rows, trainer.loss(data)):
+      replica_rows.append({'step': step, 'loss': float(np.sum(weights * per_head)),
+                           'loss_per_head': per_head.tolist()})
+
+  evaluate(0)
+  batches = train_data.batch_indices()
+  torch = trainer.torch
+  step = 0
+  while step < steps:   # up to the next evaluation, or the end
+    stop = min(steps, (step // hparams.eval_interval + 1) * hparams.eval_interval)
+    index = torch.stack([next(batches) for _ in range(stop - step)])
+    trainer.run(train_data, stop - step, index)
+    step = stop
+    if step % hparams.eval_interval == 0:
+      evaluate(step)
+  for model, checkpoint_dir in zip(trainer.export(), checkpoint_dirs):
+    model.save(checkpoint_dir)
+  return rows
 
 
 def training_loop(snapshots: np.ndarray, checkpoint_dir: str, hparams,

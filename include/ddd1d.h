@@ -614,6 +614,72 @@ DDD_API size_t ddd_train_run_workspace_bytes(const ddd_config* cfg, int batch,
 DDD_API int ddd_train_run(const ddd_config* cfg, const ddd_train_run_args* args,
                           void* stream);
 
+/* ---- replica populations ---------------------------------------------------
+ * Replaces: R runs of training.training_loop that differ in the initial seed and
+ * the learning-rate schedule (the shape in which the reference's models are
+ * compared).  ddd_train_run on R replicas of one architecture in one call: R weight
+ * vectors, R Adam states, R learning-rate rows and, with index_per_replica, R
+ * minibatch orders, over one dataset.  The replicas are a second grid dimension of
+ * the same kernels, so a step is the same number of launches whatever R is, and each
+ * replica keeps the workgroups, slabs and summation order of a solo run: replica r of
+ * a call is bit for bit ddd_train_run given replica r's weights, state, learning
+ * rates and index (weights, adam_m, adam_v, every log row and last_grad).  With
+ * error_max > 0 every replica clips from its own forward-only means.  Shared by all
+ * replicas: the dataset, nullspace / bias, first_step, the betas, epsilon, error_max,
+ * the loss constants and time_step.  Supports exactly the configurations
+ * ddd_train_run supports and refuses the others with the same status and text
+ * ("training population" as the entry point's name). */
+#define DDD_MAX_REPLICAS 64
+
+typedef struct ddd_train_population_args {
+  int32_t struct_size;   /* = sizeof(ddd_train_population_args), checked */
+  int32_t batch;         /* samples per minibatch */
+  int32_t num_rows;      /* S: rows of y / labels / baseline */
+  int32_t num_time_steps; /* T; 0 = the loss of ddd_train_loss_grad */
+  int32_t first_step;    /* optimiser steps already taken (>= 0), of every replica */
+  int32_t num_steps;     /* optimiser steps of this call (>= 1) */
+  int32_t replicas;      /* R in [1, DDD_MAX_REPLICAS] */
+  int32_t index_per_replica; /* 0: one minibatch order for all; 1: one per replica */
+  float* weights;        /* in/out [R][n_weights] (ddd_model_create layout per row) */
+  float* adam_m;         /* in/out [R][n_weights] */
+  float* adam_v;         /* in/out [R][n_weights] */
+  const float* nullspace; /* as ddd_train_args */
+  const float* bias;     /* as ddd_train_args */
+  const float* y;        /* [S][N] coarse inputs */
+  const int32_t* sample_index; /* device [num_steps][batch], or [num_steps][R][batch]
+                                  with index_per_replica.  An index outside [0, S)
+                                  makes that step's logged means NaN and, through
+                                  the update (the gradient is NaN too), the weights,
+                                  adam_m and adam_v, of the replicas that read it
+                                  only. */
+  const float* labels;   /* [S][N][H'] */
+  const float* baseline; /* [S][N][H'] */
+  const double* learning_rate; /* HOST [R][num_steps], finite and >= 0 */
+  double beta1, beta2;   /* in [0, 1) */
+  double epsilon;        /* > 0 */
+  double error_max;      /* 0 = no clipping */
+  double error_scale_abs[DDD_MAX_UNROLLED_HEADS]; /* HOST, first H' used, read with */
+  double error_scale_rel[DDD_MAX_UNROLLED_HEADS]; /* error_max > 0 only            */
+  float error_floor[DDD_MAX_UNROLLED_HEADS]; /* HOST values, first H' used */
+  float coef_abs[DDD_MAX_UNROLLED_HEADS];
+  float coef_rel[DDD_MAX_UNROLLED_HEADS];
+  float time_step;       /* the equation's time_step (T > 0) */
+  float* head_means_log; /* out [num_steps][R][2][H'] */
+  float* last_grad;      /* out [R][n_weights] or NULL: the last step's gradients */
+  void* workspace;       /* ddd_train_population_workspace_bytes(cfg, batch, T, R) bytes */
+  size_t workspace_bytes;
+} ddd_train_population_args;
+
+/* Bytes of the caller-allocated workspace of ddd_train_population_run: `replicas`
+ * times ddd_train_run_workspace_bytes(cfg, batch, T) (R times the slabs, then R
+ * coefficient tables).  0 on error, replicas outside [1, DDD_MAX_REPLICAS] included. */
+DDD_API size_t ddd_train_population_workspace_bytes(const ddd_config* cfg, int batch,
+                                                    int num_time_steps, int replicas);
+/* Enqueues num_steps optimiser steps of every replica: no stream synchronisation, no
+ * copy to the host, no graph capture.  Arguments are checked before any device work. */
+DDD_API int ddd_train_population_run(const ddd_config* cfg,
+                                     const ddd_train_population_args* args, void* stream);
+
 /* ---- differentiable evaluation --------------------------------------------
  * Replaces: tf.gradients through model.predict_result (model.py:664-697), the
  * building block of the reference's differentiable time integration
