@@ -188,6 +188,37 @@ class DDDTrainPopulationArgs(ctypes.Structure):
   ]
 
 
+class DDDEvalMetricsArgs(ctypes.Structure):
+  """struct ddd_eval_metrics_args."""
+  _fields_ = [
+      ('struct_size', ctypes.c_int32),
+      ('rows_evaluated', ctypes.c_int32),
+      ('num_rows', ctypes.c_int32),
+      ('num_time_steps', ctypes.c_int32),
+      ('replicas', ctypes.c_int32),
+      ('index_per_replica', ctypes.c_int32),
+      ('weights', ctypes.c_void_p),
+      ('nullspace', ctypes.c_void_p),
+      ('bias', ctypes.c_void_p),
+      ('y', ctypes.c_void_p),
+      ('sample_index', ctypes.c_void_p),
+      ('labels', ctypes.c_void_p),
+      ('baseline', ctypes.c_void_p),
+      ('error_floor', ctypes.c_float * MAX_UNROLLED_HEADS),
+      ('coef_abs', ctypes.c_float * MAX_UNROLLED_HEADS),
+      ('coef_rel', ctypes.c_float * MAX_UNROLLED_HEADS),
+      ('time_step', ctypes.c_float),
+      ('sums', ctypes.c_void_p),
+      ('below', ctypes.c_void_p),
+      ('predictions', ctypes.c_void_p),
+      ('workspace', ctypes.c_void_p),
+      ('workspace_bytes', ctypes.c_size_t),
+  ]
+
+
+METRIC_SUMS = 7   # float rows of ddd_eval_metrics' `sums`
+
+
 class DDDVjpArgs(ctypes.Structure):
   """struct ddd_vjp_args."""
   _fields_ = [
@@ -306,6 +337,11 @@ SIGNATURES = {
                                               ctypes.c_int, ctypes.c_int]),
     'ddd_train_population_run': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
                                                 ctypes.POINTER(DDDTrainPopulationArgs), _V]),
+    'ddd_eval_metrics_workspace_bytes': (ctypes.c_size_t,
+                                         [ctypes.POINTER(DDDConfig), ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int]),
+    'ddd_eval_metrics': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
+                                        ctypes.POINTER(DDDEvalMetricsArgs), _V]),
     'ddd_vjp_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(DDDConfig),
                                                    ctypes.c_int]),
     'ddd_result_vjp': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
@@ -771,6 +807,85 @@ def train_population_run(cfg, weights, adam_m, adam_v, y, labels, baseline, samp
   args.workspace_bytes = workspace.numel()
   check(lib.ddd_train_population_run(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
   return log, last_grad
+
+
+def eval_metrics(cfg, weights, y, labels, baseline, error_floor, coef_abs, coef_rel,
+                 num_time_steps=0, time_step=0.0, nullspace=None, bias=None,
+                 sample_index=None, rows_evaluated=None, want_predictions=False,
+                 workspace=None):
+  """ddd_eval_metrics: the sums of the evaluation metrics of R replicas in one call (two
+  launches); returns (sums [R, 7, H'] float32, below [R, H'] int32, predictions
+  [R, B, N, H'] or None), device tensors, without waiting for the device.
+
+  weights is [R, n_weights] (a tensor with more rows is taken as all of them: R =
+  weights.shape[0]); sample_index None (rows 0 .. B-1, B = rows_evaluated or S), an int32
+  device tensor [B] (shared) or [R, B]; the other arguments as train_population_run.
+  sums rows 0, 1 are the head_means of the forward-only loss call, rows 2 .. 6 and below the
+  sums calculate_metrics needs (training.metrics_from_sums)."""
+  lib = load_library()
+  torch = require_gpu()
+  steps = int(num_time_steps)
+  heads = int(labels.shape[-1])
+  if heads != cfg.num_derivatives + 1 + steps:
+    raise ValueError('labels must have num_derivatives + 1 + num_time_steps = {} channels, '
+                     'got {}'.format(cfg.num_derivatives + 1 + steps, heads))
+  if (y.dim() != 2 or tuple(labels.shape) != tuple(y.shape) + (heads,) or
+      tuple(baseline.shape) != tuple(labels.shape) or y.shape[1] != cfg.num_points):
+    raise ValueError("expected y [S, N], labels / baseline [S, N, H']")
+  n_weights = vjp_num_weights(cfg)
+  if not isinstance(weights, torch.Tensor) or weights.dim() != 2:
+    raise ValueError('weights must be [R, n_weights]')
+  replicas = int(weights.shape[0])
+  _check_f32_device('weights', weights, (replicas, n_weights))
+  for name, tensor in (('y', y), ('labels', labels), ('baseline', baseline),
+                       ('nullspace', nullspace), ('bias', bias)):
+    if tensor is not None:
+      _check_f32_device(name, tensor, tuple(tensor.shape))
+  if sample_index is not None:
+    if (not isinstance(sample_index, torch.Tensor) or sample_index.dtype != torch.int32 or
+        not sample_index.is_cuda or not sample_index.is_contiguous() or
+        sample_index.dim() not in (1, 2) or
+        (sample_index.dim() == 2 and int(sample_index.shape[0]) != replicas)):
+      raise ValueError('sample_index must be a contiguous int32 device tensor [B] or [R, B]')
+    if rows_evaluated is not None and int(rows_evaluated) != int(sample_index.shape[-1]):
+      raise ValueError('sample_index must have `rows_evaluated` entries per row')
+    rows_evaluated = int(sample_index.shape[-1])
+  elif rows_evaluated is None:
+    rows_evaluated = int(y.shape[0])
+  rows_evaluated = int(rows_evaluated)
+  ws_bytes = lib.ddd_eval_metrics_workspace_bytes(ctypes.byref(cfg), rows_evaluated, steps,
+                                                  replicas)
+  if ws_bytes == 0:
+    check(-1)
+  if workspace is None or workspace.numel() < ws_bytes:
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
+  sums = torch.empty((replicas, METRIC_SUMS, heads), dtype=torch.float32, device=y.device)
+  below = torch.empty((replicas, heads), dtype=torch.int32, device=y.device)
+  preds = (torch.empty((replicas, rows_evaluated, int(y.shape[1]), heads), dtype=torch.float32,
+                       device=y.device) if want_predictions else None)
+  args = DDDEvalMetricsArgs()
+  args.struct_size = ctypes.sizeof(DDDEvalMetricsArgs)
+  args.rows_evaluated = rows_evaluated
+  args.num_rows = int(y.shape[0])
+  args.num_time_steps = steps
+  args.replicas = replicas
+  args.index_per_replica = 1 if sample_index is not None and sample_index.dim() == 2 else 0
+  for name, tensor in (('weights', weights), ('y', y), ('labels', labels),
+                       ('baseline', baseline), ('sums', sums), ('below', below)):
+    setattr(args, name, tensor.data_ptr())
+  args.nullspace = None if nullspace is None else nullspace.data_ptr()
+  args.bias = None if bias is None else bias.data_ptr()
+  args.sample_index = None if sample_index is None else sample_index.data_ptr()
+  for h in range(heads):
+    args.error_floor[h] = float(error_floor[h])
+    args.coef_abs[h] = float(coef_abs[h])
+    args.coef_rel[h] = float(coef_rel[h])
+  args.time_step = float(time_step)
+  args.predictions = None if preds is None else preds.data_ptr()
+  args.workspace = workspace.data_ptr()
+  args.workspace_bytes = workspace.numel()
+  check(lib.ddd_eval_metrics(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
+  return sums, below, preds
 
 
 def _check_f32_device(name, tensor, shape):

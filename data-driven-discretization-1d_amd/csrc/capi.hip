@@ -35,6 +35,7 @@
 #include "rhs_stream.h"
 #include "ring_args.h"
 #include "train.h"
+#include "train_metrics.h"
 #include "train_population.h"
 #include "train_run.h"
 #include "train_unrolled.h"
@@ -1524,6 +1525,43 @@ int train_population_params(const ddd_config* cfg, int batch, int num_time_steps
   return DDD_OK;
 }
 
+// The configuration checks and kernel parameters of ddd_eval_metrics (train_metrics.h):
+// train_params (num_time_steps = 0) or train_unrolled_params under the name "evaluation
+// metrics", so exactly the configurations training admits, with its workgroups and LDS
+// plan; then this unit's slab (sums, counts and flag; the pre-activations; the stage
+// states) and the replica count.  *ws_bytes is the workspace of all replicas.
+int eval_metrics_params(const ddd_config* cfg, int rows_evaluated, int num_time_steps,
+                        int replicas, ddd::train::MetricsParams* m, size_t* ws_bytes) {
+  std::memset(m, 0, sizeof(*m));
+  ddd::train::UnrolledParams& q = m->q;
+  ddd::train::TrainParams& p = q.t;
+  size_t slabs = 0, z_floats = 0;
+  int rc;
+  if (num_time_steps == 0) {
+    rc = train_params(cfg, rows_evaluated, &p, &m->blocks, &slabs, &m->lds_bytes,
+                      "evaluation metrics");
+    q.HT = p.H;
+    if (rc == DDD_OK) z_floats = p.slab_stride - (size_t)p.n_slab;
+  } else if (num_time_steps < 0) {
+    rc = fail(DDD_ERR_INVALID_ARGUMENT, "num_time_steps = %d (>= 0)", num_time_steps);
+  } else {
+    rc = train_unrolled_params(cfg, rows_evaluated, num_time_steps, &q, &m->blocks, &slabs,
+                               &m->lds_bytes, "evaluation metrics");
+    if (rc == DDD_OK) z_floats = (size_t)q.st_off - (size_t)p.n_slab;
+  }
+  if (rc) return rc;
+  if (replicas < 1 || replicas > DDD_MAX_REPLICAS)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "replicas = %d out of range [1, %d]", replicas,
+                DDD_MAX_REPLICAS);
+  p.n_slab = ddd::train::metrics_slab_floats(q.HT);
+  q.st_off = (int)((size_t)p.n_slab + z_floats);
+  q.gi_off = 0;
+  p.slab_stride = ((size_t)q.st_off + 2 * (size_t)q.T * p.N + 3) & ~(size_t)3;
+  m->replicas = replicas;
+  *ws_bytes = (size_t)replicas * m->blocks * p.slab_stride * sizeof(float);
+  return DDD_OK;
+}
+
 // What ddd_train_run and ddd_train_population_run check and copy alike, for Args =
 // ddd_train_run_args / ddd_train_population_args (equally named fields): the arguments
 // into r, whose configuration train_run_params has filled.  ws: the bytes the workspace
@@ -2793,6 +2831,77 @@ int ddd_train_population_run(const ddd_config* cfg, const ddd_train_population_a
   pp.replicas = a->replicas;
   pp.index_per_replica = a->index_per_replica;
   DDD_HIP(ddd::train::launch_train_population(pp, static_cast<hipStream_t>(stream)));
+  return DDD_OK;
+}
+
+size_t ddd_eval_metrics_workspace_bytes(const ddd_config* cfg, int rows_evaluated,
+                                        int num_time_steps, int replicas) {
+  ddd::train::MetricsParams m;
+  size_t ws = 0;
+  if (eval_metrics_params(cfg, rows_evaluated, num_time_steps, replicas, &m, &ws)) return 0;
+  return ws;
+}
+
+int ddd_eval_metrics(const ddd_config* cfg, const ddd_eval_metrics_args* a, void* stream) {
+  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
+  if (a->struct_size != (int32_t)sizeof(ddd_eval_metrics_args))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_eval_metrics_args.struct_size = %d, library expects %d (ABI mismatch)",
+                a->struct_size, (int)sizeof(ddd_eval_metrics_args));
+  ddd::train::MetricsParams m;
+  size_t ws = 0;
+  int rc = eval_metrics_params(cfg, a->rows_evaluated, a->num_time_steps, a->replicas, &m, &ws);
+  if (rc) return rc;
+  ddd::train::UnrolledParams& q = m.q;
+  ddd::train::TrainParams& p = q.t;
+  if (a->index_per_replica != 0 && a->index_per_replica != 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "index_per_replica = %d (0 or 1)",
+                a->index_per_replica);
+  if (!a->weights || !a->y || !a->labels || !a->baseline || !a->sums || !a->below)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "weights, y, labels, baseline, sums and below must not be NULL");
+  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
+  if (projected && (!a->nullspace || !a->bias))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "nullspace/bias required for model_target 'coefficients' with "
+                "polynomial_accuracy_order > 0");
+  if (a->num_rows < 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
+  if (a->sample_index == nullptr && a->rows_evaluated > a->num_rows)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "rows_evaluated = %d > num_rows = %d without a sample_index",
+                a->rows_evaluated, a->num_rows);
+  if (a->sample_index == nullptr && a->index_per_replica)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "index_per_replica = 1 without a sample_index");
+  if (a->num_time_steps > 0 && !std::isfinite(a->time_step))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
+  if (a->workspace == nullptr || a->workspace_bytes < ws)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "workspace of %zu bytes given, ddd_eval_metrics_workspace_bytes = %zu",
+                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws);
+  for (int h = 0; h < q.HT; ++h) {
+    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
+        !std::isfinite(a->coef_rel[h]))
+      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
+    q.floor[h] = a->error_floor[h];
+    q.coef_abs[h] = a->coef_abs[h];
+    q.coef_rel[h] = a->coef_rel[h];
+  }
+  p.weights = a->weights;
+  p.nullspace = projected ? a->nullspace : nullptr;
+  p.bias = projected ? a->bias : nullptr;
+  p.y = a->y;
+  p.sample_index = a->sample_index;
+  p.index_stride = a->index_per_replica ? p.batch : 0;
+  p.rows = a->num_rows;
+  p.labels = a->labels;
+  p.baseline = a->baseline;
+  p.predictions = a->predictions;
+  p.ws = static_cast<float*>(a->workspace);
+  q.dt = a->time_step;
+  m.sums = a->sums;
+  m.below = a->below;
+  DDD_HIP(ddd::train::launch_eval_metrics(m, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }
 

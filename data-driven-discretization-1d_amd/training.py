@@ -12,8 +12,14 @@ the same gradient with Adam fused into its slab sum, error_max decided on the de
 PopulationTrainer / training_population train R replicas of one architecture -- R initial
 seeds, R learning-rate schedules -- in one such call (ddd_train_population_run,
 csrc/train_population.hip): the replicas are a second grid dimension of the same kernels.
+Inferer evaluates a trainer or a population over a whole dataset in one call
+(ddd_eval_metrics, csrc/train_metrics.hip) and returns the reference's calculate_metrics
+(training.py:433-491) per replica; training_loop / training_population(metrics=True) log
+them for both splits as the reference's loop does.
 """
 import copy
+import json
+import logging
 import os
 from typing import Dict, List, Sequence
 
@@ -370,25 +376,209 @@ class PopulationTrainer(object):
     return per_head
 
   def loss(self, dataset) -> np.ndarray:
-    """loss_per_head [R, 2, channel] over the whole dataset, forward only (one
-    ddd_train_loss_grad / ddd_train_unrolled_loss_grad call per replica)."""
-    return np.stack([trainer.loss_and_grad(dataset, want_grad=False)[0]
-                     for trainer in self.trainers])
+    """loss_per_head [R, 2, channel] over the whole dataset, forward only: one
+    ddd_eval_metrics call and one host read for all replicas.  Its two loss rows are bit
+    for bit the head_means of a forward-only ddd_train_loss_grad /
+    ddd_train_unrolled_loss_grad call per replica."""
+    sums, _, _ = Inferer(dataset, self).run_async()
+    return _scaled_loss_per_head(sums, self.hparams)
 
   def export(self) -> List[model_lib.LearnedStencilModel]:
     """The current weights as R LearnedStencilModels."""
     return [trainer.export() for trainer in self.trainers]
 
 
+def _scaled_loss_per_head(sums, hparams) -> np.ndarray:
+  """[R, 2, channel] float64: the two loss rows of ddd_eval_metrics' sums (one host read),
+  scaled by error_scale and clipped at error_max as Trainer.loss_and_grad returns them."""
+  scale = np.array(hparams.error_scale, np.float64).reshape(2, -1)
+  per_head = sums[:, :2].double().cpu().numpy() * scale
+  if hparams.error_max:
+    per_head = np.where(per_head < hparams.error_max, per_head, hparams.error_max)
+  return per_head
+
+
+METRIC_NAMES = ('mae', 'rms_error', 'mean_abs_relative_error', 'frac_below_baseline')
+
+
+def _target_metrics(mae, rms_error, geometric, below, equation_type) -> Dict[str, float]:
+  """The per-target keys of calculate_metrics from per-channel vectors: one entry per
+  space derivative and 'u_t', then 'u(t)' = the mean over the integrated heads."""
+  per_channel = dict(zip(METRIC_NAMES, (mae, rms_error, geometric, below)))
+  targets = list(equation_type.DERIVATIVE_NAMES) + ['u_t']
+  if len(mae) < len(targets):
+    raise ValueError('{} channels, {} targets'.format(len(mae), len(targets)))
+  metrics = {}
+  for i, target in enumerate(targets):
+    for name in METRIC_NAMES:
+      metrics['{}/{}'.format(name, target)] = per_channel[name][i]
+  if len(mae) > len(targets):
+    for name in METRIC_NAMES:
+      metrics[name + '/u(t)'] = per_channel[name][len(targets):].mean()
+  return metrics
+
+
+def calculate_metrics(data: Dict[str, np.ndarray], equation_type) -> Dict[str, float]:
+  """training.py:433-491 on host arrays: data holds 'labels', 'baseline' and
+  'predictions' [examples, x, channel] and scalar 'loss...' entries.  Per target the MAE
+  and RMS error relative to the baseline's, the geometric-mean relative error and the
+  fraction of points whose squared error is below the baseline's; 'count' examples; the
+  loss entries as floats."""
+  labels = np.asarray(data['labels'])
+  baseline = np.asarray(data['baseline'])
+  predictions = np.asarray(data['predictions'])
+  labels = model_lib.align_labels(labels, baseline)
+  err, base = labels - predictions, labels - baseline
+  over = (0, 1)
+  mae = np.mean(np.abs(err), axis=over) / np.mean(np.abs(base), axis=over)
+  rms_error = np.sqrt(np.mean(err ** 2, axis=over) / np.mean(base ** 2, axis=over))
+  ratio = np.maximum(np.abs(err), 1e-8) / np.maximum(np.abs(base), 1e-8)
+  geometric = np.exp(np.mean(np.log(ratio), axis=over))
+  below = np.mean(err ** 2 < base ** 2, axis=over)
+  metrics = {'count': len(labels)}
+  metrics.update({k: float(v) for k, v in data.items() if 'loss' in k})
+  metrics.update(_target_metrics(mae, rms_error, geometric, below, equation_type))
+  return metrics
+
+
+def metrics_from_sums(sums, below, count: int, num_points: int, equation_type,
+                      losses: Dict[str, float] = None) -> Dict[str, float]:
+  """calculate_metrics from the sums of ddd_eval_metrics for one replica: sums
+  [7, channel] (rows 2 .. 6: sum |l - p|, sum |l - b|, sum (l - p)^2, sum (l - b)^2,
+  sum log max(|l - p|, 1e-8) - log max(|l - b|, 1e-8); rows 0, 1 are not read), below
+  [channel] points under the baseline, over `count` examples of num_points points.  The
+  divisions, the root and the exponential are taken here, in float64.  losses: the
+  'loss...' entries to carry."""
+  sums = np.asarray(sums, np.float64)
+  total = float(count) * float(num_points)
+  mae = sums[2] / sums[3]
+  rms_error = np.sqrt(sums[4] / sums[5])
+  geometric = np.exp(sums[6] / total)
+  fraction = np.asarray(below, np.float64) / total
+  metrics = {'count': int(count)}
+  metrics.update({k: float(v) for k, v in (losses or {}).items()})
+  metrics.update(_target_metrics(mae, rms_error, geometric, fraction, equation_type))
+  return metrics
+
+
+def metrics_one_linear(metrics: Dict[str, float]) -> str:
+  """training.py:494-507: one line of the loss and, per target in key order, the MAE,
+  the geometric-mean relative error and the fraction below the baseline."""
+  def matching(like):
+    return '/'.join('{}={:1.4f}'.format(k.split('/')[-1], v)
+                    for k, v in sorted(metrics.items()) if like in k)
+  return 'loss: {:1.7f}, abs_error: {}, rel_error: {}, below_baseline: {}'.format(
+      metrics['loss'], matching('mae'), matching('mean_abs_relative_error'),
+      matching('frac_below_baseline'))
+
+
+def metrics_to_dataframe(logged_metrics):
+  """training.py:537-547: [(step, test_metrics, train_metrics)] -> one DataFrame row per
+  evaluation, keys prefixed 'test_' / 'train_', plus 'step'."""
+  import pandas as pd
+  return pd.DataFrame([_metrics_row(*logged) for logged in logged_metrics])
+
+
+def _metrics_row(step, test_metrics, train_metrics) -> Dict[str, float]:
+  row = {'test_' + k: v for k, v in test_metrics.items()}
+  row.update({'train_' + k: v for k, v in train_metrics.items()})
+  row['step'] = step
+  return row
+
+
+def loss_metrics(per_head: np.ndarray, hparams, equation_type) -> Dict[str, float]:
+  """training.py:279-297 from loss_per_head [2, channel]: 'loss' (weighted_loss) and the
+  means of its space-derivative, time-derivative and integrated-solution entries."""
+  space, time, integrated = model_lib.result_unstack(per_head, equation_type)
+  losses = {'loss': float(model_lib.weighted_loss(per_head, hparams)),
+            'loss/space_derivatives': float(np.mean(space)),
+            'loss/time_derivative': float(np.mean(time))}
+  if integrated is not None:
+    losses['loss/integrated_solution'] = float(np.mean(integrated))
+  return losses
+
+
+class Inferer(object):
+  """training.py:253-314 for a Trainer or a PopulationTrainer: the evaluation metrics of
+  every replica over the whole `dataset` (a DeviceDataset) in one ddd_eval_metrics call.
+
+  'loss' and 'loss/*' are computed from the means over the whole dataset.  The reference
+  averages the per-batch means with equal weight (tf.metrics.mean over batches); the two
+  agree when the batches are equal in size, and differ by the weight of a shorter last
+  batch otherwise."""
+
+  def __init__(self, dataset, trainer):
+    self.dataset = dataset
+    self.trainer = trainer
+    self.population = isinstance(trainer, PopulationTrainer)
+    self.hparams = trainer.hparams
+    self.equation_type = equations_lib.equation_type_from_hparams(self.hparams)
+
+  def run_async(self, want_predictions: bool = False):
+    """Enqueues the call; returns the device tensors (sums [R, 7, channel], below
+    [R, channel], predictions [R, examples, x, channel] or None) without waiting, so that
+    several stretches and evaluations can be enqueued before one read."""
+    trainer, dataset, hp = self.trainer, self.dataset, self.hparams
+    first = trainer.trainers[0] if self.population else trainer
+    weights = trainer.weights if self.population else trainer.weights.detach()[None]
+    heads = int(dataset.labels.shape[-1])
+    floor, coef_abs, coef_rel = first.coefficients(heads)
+    steps = hp.num_time_steps or 0
+    model = trainer.models[0] if self.population else trainer.model
+    return _lib.eval_metrics(
+        first.cfg, weights, dataset.inputs, dataset.labels, dataset.baseline, floor, coef_abs,
+        coef_rel, num_time_steps=steps,
+        time_step=model.equation.time_step if steps else 0.0, nullspace=first.nullspace,
+        bias=first.bias, want_predictions=want_predictions)
+
+  def metrics(self, sums, below) -> List[Dict[str, float]]:
+    """The metrics dicts of run_async's tensors: one host read, then float64."""
+    per_head = _scaled_loss_per_head(sums, self.hparams)
+    sums = sums.double().cpu().numpy()
+    below = below.cpu().numpy()
+    return [metrics_from_sums(
+        sums[r], below[r], self.dataset.num_examples, int(self.dataset.inputs.shape[1]),
+        self.equation_type, loss_metrics(per_head[r], self.hparams, self.equation_type))
+            for r in range(sums.shape[0])]
+
+  def run(self) -> List[Dict[str, float]]:
+    """One metrics dict per replica, with the keys of calculate_metrics."""
+    sums, below, _ = self.run_async()
+    return self.metrics(sums, below)
+
+
+def select_replica(rows, key: str):
+  """(replica, value) of the best replica at the last evaluation: the smallest last-row
+  value of `key` ('loss' or a metric key such as 'test_mae/u_t'), the largest for a
+  'frac_below_baseline' key; NaN never wins; ties go to the lowest index."""
+  values = []
+  for replica_rows in rows:
+    if key not in replica_rows[-1]:
+      raise KeyError('select = {!r}: the rows have {}'.format(key, sorted(replica_rows[-1])))
+    values.append(float(replica_rows[-1][key]))
+  sign = -1.0 if 'frac_below_baseline' in key else 1.0
+  ranked = [sign * v if np.isfinite(v) else np.inf for v in values]
+  best = int(np.argmin(ranked))
+  return best, values[best]
+
+
 def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], hparams,
                         init_seeds: Sequence[int], learning_rates=None, seed: int = 0,
-                        num_steps: int = None) -> List[List[Dict[str, float]]]:
+                        num_steps: int = None, metrics: bool = False, select: str = None):
   """training_loop(..., seed=seed, fused=True) for R replicas at once: the same dataset,
   train / validation split and minibatch order; replica r starts from
   LearnedStencilModel(coarse, hparams, init_seed=init_seeds[r]) and follows
   learning_rates[r] (default: hparams.learning_rates); every stretch between two
   evaluations is one PopulationTrainer.run.  Writes hparams.json + model.npz to
-  checkpoint_dirs[r]; returns one list of metric rows per replica."""
+  checkpoint_dirs[r]; returns one list of metric rows per replica.
+
+  metrics: every evaluation also runs an Inferer over the validation and the training
+  split (one call each for all replicas) and adds their 'test_*' / 'train_*' entries
+  (metrics_to_dataframe's keys) to the rows; the test metrics of every replica are logged
+  with metrics_one_linear.  select: 'loss' or, with metrics, any key of the rows such as
+  'test_mae/u_t': returns (rows, best) with best the index of the best replica at the last
+  evaluation (select_replica), and writes best.json {'replica', 'key', 'value',
+  'checkpoint_dir'} next to the checkpoint directories."""
   if len(checkpoint_dirs) != len(init_seeds):
     raise ValueError('one checkpoint directory per init seed')
   hparams = copy.deepcopy(hparams)
@@ -408,11 +598,27 @@ def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], h
   weights = model_lib.loss_weights(hparams, int(train_data.labels.shape[-1]))
   rows = [[] for _ in init_seeds]
 
+  inferers = None
+  if metrics:   # the reference's two Inferers: each split without rolls or noise
+    train_eval = model_lib.make_dataset(snapshots, hparams, model_lib.Dataset.TRAINING,
+                                        repeat=False, evaluation=True, seed=seed)
+    inferers = (Inferer(valid_data if valid_data.num_examples else train_eval, trainer),
+                Inferer(train_eval, trainer))
+
   def evaluate(step):
     data = valid_data if valid_data.num_examples else train_data
-    for replica_rows, per_head in zip(rows, trainer.loss(data)):
-      replica_rows.append({'step': step, 'loss': float(np.sum(weights * per_head)),
-                           'loss_per_head': per_head.tolist()})
+    logged = None
+    if metrics:   # both splits enqueued, then read
+      pending = [inferer.run_async() for inferer in inferers]
+      logged = [inferer.metrics(sums, below)
+                for inferer, (sums, below, _) in zip(inferers, pending)]
+    for r, (replica_rows, per_head) in enumerate(zip(rows, trainer.loss(data))):
+      row = {'step': step, 'loss': float(np.sum(weights * per_head)),
+             'loss_per_head': per_head.tolist()}
+      if metrics:
+        row.update(_metrics_row(step, logged[0][r], logged[1][r]))
+        logging.info('replica %d: %s', r, metrics_one_linear(logged[0][r]))
+      replica_rows.append(row)
 
   evaluate(0)
   batches = train_data.batch_indices()
@@ -427,18 +633,28 @@ def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], h
       evaluate(step)
   for model, checkpoint_dir in zip(trainer.export(), checkpoint_dirs):
     model.save(checkpoint_dir)
-  return rows
+  if select is None:
+    return rows
+  best, value = select_replica(rows, select)
+  parent = os.path.dirname(os.path.abspath(checkpoint_dirs[best]))
+  with open(os.path.join(parent, 'best.json'), 'w') as f:
+    json.dump({'replica': best, 'key': select, 'value': value,
+               'checkpoint_dir': checkpoint_dirs[best]}, f)
+  return rows, best
 
 
 def training_loop(snapshots: np.ndarray, checkpoint_dir: str, hparams,
                   seed: int = 0, num_steps: int = None,
-                  fused: bool = False) -> List[Dict[str, float]]:
+                  fused: bool = False, metrics: bool = False) -> List[Dict[str, float]]:
   """training.py:570-636: trains on fine snapshots [examples, x], writes hparams.json +
   model.npz (LearnedStencilModel.save) to checkpoint_dir and returns one metrics row
   per eval_interval steps: the validation loss and loss per head.  num_steps defaults
   to learning_stops[-1].  fused: every stretch between two evaluations is one
   Trainer.run call (the same minibatch order) instead of eval_interval Trainer.step
-  calls."""
+  calls.  metrics: every evaluation also runs an Inferer over the validation and the
+  training split, as the reference's loop does, adds their 'test_*' / 'train_*' entries
+  (metrics_to_dataframe's keys) to the row and logs metrics_one_linear of the test
+  metrics."""
   hparams = copy.deepcopy(hparams)
   _checker(hparams)(hparams)
   train_data = set_data_dependent_hparams(hparams, snapshots, seed)
@@ -453,11 +669,25 @@ def training_loop(snapshots: np.ndarray, checkpoint_dir: str, hparams,
   weights = model_lib.loss_weights(hparams, int(train_data.labels.shape[-1]))
   rows = []
 
+  inferers = None
+  if metrics:   # the reference's two Inferers: each split without rolls or noise
+    train_eval = model_lib.make_dataset(snapshots, hparams, model_lib.Dataset.TRAINING,
+                                        repeat=False, evaluation=True, seed=seed)
+    inferers = (Inferer(valid_data if valid_data.num_examples else train_eval, trainer),
+                Inferer(train_eval, trainer))
+
   def evaluate(step):
     data = valid_data if valid_data.num_examples else train_data
     per_head, _, _ = trainer.loss_and_grad(data, want_grad=False)
-    rows.append({'step': step, 'loss': float(np.sum(weights * per_head)),
-                 'loss_per_head': per_head.tolist()})
+    row = {'step': step, 'loss': float(np.sum(weights * per_head)),
+           'loss_per_head': per_head.tolist()}
+    if metrics:   # both splits enqueued, then read
+      pending = [inferer.run_async() for inferer in inferers]
+      test, train = [inferer.metrics(sums, below)[0]
+                     for inferer, (sums, below, _) in zip(inferers, pending)]
+      row.update(_metrics_row(step, test, train))
+      logging.info(metrics_one_linear(test))
+    rows.append(row)
 
   evaluate(0)
   batches = train_data.batch_indices()

@@ -680,6 +680,65 @@ DDD_API size_t ddd_train_population_workspace_bytes(const ddd_config* cfg, int b
 DDD_API int ddd_train_population_run(const ddd_config* cfg,
                                      const ddd_train_population_args* args, void* stream);
 
+/* ---- evaluation on the device -----------------------------------------------
+ * Replaces: training.Inferer.run + calculate_metrics (training.py:253-314,
+ * 433-491) for R replicas of one architecture over one dataset: forward only,
+ * two launches whatever R is.  Per replica and head h of the H' =
+ * num_derivatives + 1 + num_time_steps heads, over the rows evaluated and their
+ * N points, with prediction p, label l and baseline b:
+ *   sums[r][0][h], sums[r][1][h]  head_means of ddd_train_loss_grad /
+ *                                 ddd_train_unrolled_loss_grad (grad = NULL) on the
+ *                                 same rows, bit for bit (means over rows N)
+ *   sums[r][2][h], sums[r][3][h]  sum |l - p|, sum |l - b|
+ *   sums[r][4][h], sums[r][5][h]  sum (l - p)^2, sum (l - b)^2
+ *   sums[r][6][h]                 sum log(max(|l - p|, 1e-8)) - log(max(|l - b|, 1e-8))
+ *   below[r][h]                   points with (l - p)^2 < (l - b)^2, counted in int32
+ *                                 (rows_evaluated N < 2^31)
+ * all in float32, each workgroup's samples in a fixed order and the workgroups'
+ * partial sums in a fixed order (no atomics): equal inputs give equal bits, and
+ * replica r of a call equals the call on replica r alone.  The ratios, roots and
+ * exponentials of the metrics are the caller's.  Supports exactly the
+ * configurations ddd_train_loss_grad supports and refuses the others with the same
+ * status and text ("evaluation metrics" as the entry point's name). */
+typedef struct ddd_eval_metrics_args {
+  int32_t struct_size;   /* = sizeof(ddd_eval_metrics_args), checked */
+  int32_t rows_evaluated; /* B: samples evaluated per replica */
+  int32_t num_rows;      /* S: rows of y / labels / baseline */
+  int32_t num_time_steps; /* T; 0 = the heads of ddd_train_loss_grad */
+  int32_t replicas;      /* R in [1, DDD_MAX_REPLICAS] */
+  int32_t index_per_replica; /* 0: one sample_index for all; 1: one per replica */
+  const float* weights;  /* [R][n_weights] (ddd_model_create layout per row) */
+  const float* nullspace; /* as ddd_train_args */
+  const float* bias;     /* as ddd_train_args */
+  const float* y;        /* [S][N] coarse inputs */
+  const int32_t* sample_index; /* device [B], or [R][B] with index_per_replica, or NULL
+                                  (rows 0 .. B-1, B <= S).  An index outside [0, S)
+                                  makes the sums NaN and the counts -1 of the replicas
+                                  that read it, and that sample's predictions row NaN;
+                                  no input is read for it. */
+  const float* labels;   /* [S][N][H'] */
+  const float* baseline; /* [S][N][H'] */
+  float error_floor[DDD_MAX_UNROLLED_HEADS]; /* HOST values, first H' used */
+  float coef_abs[DDD_MAX_UNROLLED_HEADS];    /* (accepted for symmetry with training; */
+  float coef_rel[DDD_MAX_UNROLLED_HEADS];    /*  the sums do not depend on them)      */
+  float time_step;       /* the equation's time_step (T > 0) */
+  float* sums;           /* out [R][7][H'] */
+  int32_t* below;        /* out [R][H'] */
+  float* predictions;    /* out [R][B][N][H'] or NULL */
+  void* workspace;       /* ddd_eval_metrics_workspace_bytes(cfg, B, T, R) bytes */
+  size_t workspace_bytes;
+} ddd_eval_metrics_args;
+
+/* Bytes of the caller-allocated workspace of ddd_eval_metrics (per replica and
+ * workgroup the partial sums, the scratch of the forward pass and the stage states).
+ * 0 on error, replicas outside [1, DDD_MAX_REPLICAS] included. */
+DDD_API size_t ddd_eval_metrics_workspace_bytes(const ddd_config* cfg, int rows_evaluated,
+                                                int num_time_steps, int replicas);
+/* Enqueues the two launches: no stream synchronisation, no copy to the host, no graph
+ * capture.  Arguments are checked before any device work. */
+DDD_API int ddd_eval_metrics(const ddd_config* cfg, const ddd_eval_metrics_args* args,
+                             void* stream);
+
 /* ---- differentiable evaluation --------------------------------------------
  * Replaces: tf.gradients through model.predict_result (model.py:664-697), the
  * building block of the reference's differentiable time integration
