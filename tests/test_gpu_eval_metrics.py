@@ -33,6 +33,7 @@ CASES = {
     # every case and replica (one or no point of a case).
     'burgers-cons-N32-T0': ('burgers', True, 32, dict(filter_size=32), 0, ROWS, None),
     'burgers-cons-N32-T2-515': ('burgers', True, 32, dict(filter_size=32), 2, 515, 'shared'),
+    'burgers-cons-N128-T2': ('burgers', True, 128, dict(filter_size=32), 2, ROWS, 'shared'),
     'ks-N24-f16-T0-515': ('ks', False, 24, dict(filter_size=16), 0, 515, 'replica'),
     'ks-N24-f16-T2': ('ks', False, 24, dict(filter_size=16), 2, ROWS, 'replica'),
     'kdv-N40-T0': ('kdv', False, 40, dict(), 0, ROWS, 'shared'),

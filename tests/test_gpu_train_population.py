@@ -105,6 +105,8 @@ def _assert_replicas_are_solo_runs(s, weights, m, v, index, rates, replicas=None
     ('burgers', 32, dict(), 700, 600, 2, 1, True),
     # 4. the VALU-only route at the LDS limit
     ('ks', 256, dict(kernel_size=7, filter_size=64, num_layers=1), 12, 6, 2, 1, True),
+    # 5. the MFMA route on all four wavefronts: the replicas' staged kernels and biases
+    ('burgers', 128, dict(), 12, 6, 2, 2, True),
 ])
 def test_replicas_are_solo_runs(equation, n, overrides, rows, batch, replicas, steps,
                                 per_replica):

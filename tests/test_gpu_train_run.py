@@ -51,6 +51,9 @@ def _rel(got, want):
     ('ks', False, 256, dict(kernel_size=7, filter_size=64, num_layers=1), 12, 6),
     # more samples than slabs (512 workgroups)
     ('burgers', False, 32, dict(), 700, 600),
+    # the MFMA route on all four wavefronts (four 32-row tiles); last, so that the
+    # cases above keep their ids
+    ('burgers', False, 128, dict(), 12, 6),
 ])
 def test_one_step_gradient_and_log_are_exact(equation, conservative, n, overrides, rows, batch):
   model = _model(equation, conservative, n, overrides)
