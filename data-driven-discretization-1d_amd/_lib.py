@@ -219,6 +219,52 @@ class DDDEvalMetricsArgs(ctypes.Structure):
 METRIC_SUMS = 7   # float rows of ddd_eval_metrics' `sums`
 
 
+class DDDRolloutReferenceArgs(ctypes.Structure):
+  """struct ddd_rollout_reference_args."""
+  _fields_ = [
+      ('struct_size', ctypes.c_int32),
+      ('num_samples', ctypes.c_int32),
+      ('num_times', ctypes.c_int32),
+      ('num_points_exact', ctypes.c_int32),
+      ('num_points', ctypes.c_int32),
+      ('y_exact', ctypes.c_void_p),
+      ('exact_low', ctypes.c_void_p),
+  ]
+
+
+class DDDRolloutScoresArgs(ctypes.Structure):
+  """struct ddd_rollout_scores_args."""
+  _fields_ = [
+      ('struct_size', ctypes.c_int32),
+      ('replicas', ctypes.c_int32),
+      ('num_times', ctypes.c_int32),
+      ('num_samples', ctypes.c_int32),
+      ('num_points', ctypes.c_int32),
+      ('num_quantiles', ctypes.c_int32),
+      ('num_stop_times', ctypes.c_int32),
+      ('dtype', ctypes.c_int32),
+      ('y_model', ctypes.c_void_p),
+      ('exact_low', ctypes.c_void_p),
+      ('times', ctypes.c_void_p),
+      ('max_error', ctypes.c_void_p),
+      ('frac_good', ctypes.c_void_p),
+      ('stop_times', ctypes.c_void_p),
+      ('mae', ctypes.c_void_p),
+      ('survival', ctypes.c_void_p),
+      ('row_abs_sum', ctypes.c_void_p),
+      ('good', ctypes.c_void_p),
+      ('workspace', ctypes.c_void_p),
+      ('workspace_bytes', ctypes.c_size_t),
+  ]
+
+
+ROLLOUT_MAX_QUANTILES = 8    # DDD_ROLLOUT_MAX_QUANTILES
+ROLLOUT_MAX_STOP_TIMES = 16  # DDD_ROLLOUT_MAX_STOP_TIMES
+ROLLOUT_MAX_POINTS = 1024    # DDD_ROLLOUT_MAX_POINTS
+ROLLOUT_MAX_FACTOR = 128     # DDD_ROLLOUT_MAX_FACTOR
+ROLLOUT_F64, ROLLOUT_F32 = 0, 1
+
+
 class DDDVjpArgs(ctypes.Structure):
   """struct ddd_vjp_args."""
   _fields_ = [
@@ -342,6 +388,10 @@ SIGNATURES = {
                                           ctypes.c_int, ctypes.c_int]),
     'ddd_eval_metrics': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
                                         ctypes.POINTER(DDDEvalMetricsArgs), _V]),
+    'ddd_rollout_reference': (ctypes.c_int, [ctypes.POINTER(DDDRolloutReferenceArgs), _V]),
+    'ddd_rollout_scores_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int,
+                                                              ctypes.c_int, ctypes.c_int]),
+    'ddd_rollout_scores': (ctypes.c_int, [ctypes.POINTER(DDDRolloutScoresArgs), _V]),
     'ddd_vjp_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(DDDConfig),
                                                    ctypes.c_int]),
     'ddd_result_vjp': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
@@ -886,6 +936,103 @@ def eval_metrics(cfg, weights, y, labels, baseline, error_floor, coef_abs, coef_
   args.workspace_bytes = workspace.numel()
   check(lib.ddd_eval_metrics(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
   return sums, below, preds
+
+
+def _check_device(name, tensor, dtype, shape):
+  torch = _torch()
+  if (not isinstance(tensor, torch.Tensor) or tensor.dtype != dtype or not tensor.is_cuda or
+      not tensor.is_contiguous()):
+    raise ValueError('{} must be a contiguous {} device tensor'.format(name, dtype))
+  if shape is not None and tuple(tensor.shape) != tuple(shape):
+    raise ValueError('{} has shape {}, expected {}'.format(name, tuple(tensor.shape),
+                                                           tuple(shape)))
+
+
+def rollout_reference(y_exact, num_points: int):
+  """ddd_rollout_reference: y_exact [S, T, X] float64 on the device -> exact_low [T, S, N]
+  float64, the block means of duckarray.resample_mean bit for bit, in the layout of the
+  integrators' trajectories.  One launch on the current stream; nothing waits."""
+  lib = load_library()
+  torch = require_gpu()
+  _check_device('y_exact', y_exact, torch.float64, None)
+  if y_exact.dim() != 3:
+    raise ValueError('y_exact must be [sample, time, x]')
+  samples, num_times, fine = (int(v) for v in y_exact.shape)
+  exact_low = torch.empty((num_times, samples, int(num_points)), dtype=torch.float64,
+                          device=y_exact.device)
+  args = DDDRolloutReferenceArgs()
+  args.struct_size = ctypes.sizeof(DDDRolloutReferenceArgs)
+  args.num_samples = samples
+  args.num_times = num_times
+  args.num_points_exact = fine
+  args.num_points = int(num_points)
+  args.y_exact = y_exact.data_ptr()
+  args.exact_low = exact_low.data_ptr()
+  check(lib.ddd_rollout_reference(ctypes.byref(args), current_stream()))
+  return exact_low
+
+
+def rollout_scores(y_model, exact_low, times, max_error, frac_good, stop_times,
+                   want_rows=False, workspace=None):
+  """ddd_rollout_scores: y_model [R, T, S, N] (float64 or float32) against exact_low
+  [T, S, N]; returns device tensors (mae [R, K, S], survival [R, Q, S]) and, with
+  want_rows, also (row_abs_sum [R, T, S], good [R, Q, T, S] uint8), without waiting for the
+  device.  times, max_error, frac_good and stop_times are host sequences."""
+  lib = load_library()
+  torch = require_gpu()
+  if not isinstance(y_model, torch.Tensor) or y_model.dim() != 4:
+    raise ValueError('y_model must be a device tensor [replica, time, sample, x]')
+  if y_model.dtype not in (torch.float64, torch.float32):
+    raise ValueError('y_model must be float64 or float32')
+  _check_device('y_model', y_model, y_model.dtype, None)
+  replicas, num_times, samples, points = (int(v) for v in y_model.shape)
+  _check_device('exact_low', exact_low, torch.float64, (num_times, samples, points))
+  times = np.ascontiguousarray(times, dtype=np.float64)
+  max_error = np.ascontiguousarray(max_error, dtype=np.float64)
+  frac_good = np.ascontiguousarray(frac_good, dtype=np.float64)
+  stop_times = np.ascontiguousarray(stop_times, dtype=np.float64)
+  if times.shape != (num_times,):
+    raise ValueError('times must have one entry per row of y_model')
+  if max_error.ndim != 1 or max_error.shape != frac_good.shape or stop_times.ndim != 1:
+    raise ValueError('max_error and frac_good [Q], stop_times [K]')
+  nq, nk = int(max_error.size), int(stop_times.size)
+  device = y_model.device
+  ws_bytes = lib.ddd_rollout_scores_workspace_bytes(replicas, num_times, samples, nq)
+  if ws_bytes == 0:
+    check(-1)
+  if workspace is None or workspace.numel() < ws_bytes:
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+  mae = torch.empty((replicas, nk, samples), dtype=torch.float64, device=device)
+  survival = torch.empty((replicas, nq, samples), dtype=torch.float64, device=device)
+  rows = good = None
+  if want_rows:
+    rows = torch.empty((replicas, num_times, samples), dtype=torch.float64, device=device)
+    good = torch.empty((replicas, nq, num_times, samples), dtype=torch.uint8, device=device)
+  args = DDDRolloutScoresArgs()
+  args.struct_size = ctypes.sizeof(DDDRolloutScoresArgs)
+  args.replicas = replicas
+  args.num_times = num_times
+  args.num_samples = samples
+  args.num_points = points
+  args.num_quantiles = nq
+  args.num_stop_times = nk
+  args.dtype = ROLLOUT_F32 if y_model.dtype == torch.float32 else ROLLOUT_F64
+  args.y_model = y_model.data_ptr()
+  args.exact_low = exact_low.data_ptr()
+  args.times = times.ctypes.data
+  args.max_error = max_error.ctypes.data
+  args.frac_good = frac_good.ctypes.data
+  args.stop_times = stop_times.ctypes.data
+  args.mae = mae.data_ptr()
+  args.survival = survival.data_ptr()
+  args.row_abs_sum = None if rows is None else rows.data_ptr()
+  args.good = None if good is None else good.data_ptr()
+  args.workspace = workspace.data_ptr()
+  args.workspace_bytes = workspace.numel()
+  check(lib.ddd_rollout_scores(ctypes.byref(args), current_stream()))
+  if want_rows:
+    return mae, survival, rows, good
+  return mae, survival
 
 
 def _check_f32_device(name, tensor, shape):

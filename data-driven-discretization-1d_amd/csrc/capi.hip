@@ -34,6 +34,7 @@
 #include "rhs_spectral.h"
 #include "rhs_stream.h"
 #include "ring_args.h"
+#include "rollout_scores.h"
 #include "train.h"
 #include "train_metrics.h"
 #include "train_population.h"
@@ -2902,6 +2903,142 @@ int ddd_eval_metrics(const ddd_config* cfg, const ddd_eval_metrics_args* a, void
   m.sums = a->sums;
   m.below = a->below;
   DDD_HIP(ddd::train::launch_eval_metrics(m, static_cast<hipStream_t>(stream)));
+  return DDD_OK;
+}
+
+static_assert(ddd::rollout::kMaxQuantiles == DDD_ROLLOUT_MAX_QUANTILES &&
+                  ddd::rollout::kMaxStopTimes == DDD_ROLLOUT_MAX_STOP_TIMES &&
+                  ddd::rollout::kMaxPoints == DDD_ROLLOUT_MAX_POINTS &&
+                  ddd::rollout::kMaxFactor == DDD_ROLLOUT_MAX_FACTOR,
+              "rollout_scores.h / ddd1d.h");
+
+int ddd_rollout_reference(const ddd_rollout_reference_args* a, void* stream) {
+  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
+  if (a->struct_size != (int32_t)sizeof(ddd_rollout_reference_args))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_rollout_reference_args.struct_size = %d, library expects %d (ABI mismatch)",
+                a->struct_size, (int)sizeof(ddd_rollout_reference_args));
+  if (a->num_samples < 1 || a->num_times < 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_samples = %d, num_times = %d (both >= 1)",
+                a->num_samples, a->num_times);
+  if (a->num_points < 1 || a->num_points > DDD_ROLLOUT_MAX_POINTS)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_points = %d out of range [1, %d]", a->num_points,
+                DDD_ROLLOUT_MAX_POINTS);
+  if (a->num_points_exact < a->num_points || a->num_points_exact % a->num_points != 0)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "num_points_exact = %d is not a multiple of num_points = %d",
+                a->num_points_exact, a->num_points);
+  const int factor = a->num_points_exact / a->num_points;
+  if (factor > DDD_ROLLOUT_MAX_FACTOR)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "num_points_exact / num_points = %d out of range [1, %d]", factor,
+                DDD_ROLLOUT_MAX_FACTOR);
+  if (!a->y_exact || !a->exact_low)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "y_exact and exact_low must not be NULL");
+  const size_t outputs = (size_t)a->num_samples * a->num_times * a->num_points;
+  if ((outputs + ddd::rollout::kThreads - 1) / ddd::rollout::kThreads > 0x7fffffffu)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "num_samples num_times num_points = %zu: too many for one launch", outputs);
+  ddd::rollout::ReferenceParams p;
+  p.y_exact = a->y_exact;
+  p.exact_low = a->exact_low;
+  p.S = a->num_samples;
+  p.T = a->num_times;
+  p.N = a->num_points;
+  p.f = factor;
+  DDD_HIP(ddd::rollout::launch_reference(p, static_cast<hipStream_t>(stream)));
+  return DDD_OK;
+}
+
+namespace {
+
+int rollout_sizes(int replicas, int num_times, int num_samples, int num_quantiles) {
+  if (replicas < 1 || replicas > DDD_MAX_REPLICAS)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "replicas = %d out of range [1, %d]", replicas,
+                DDD_MAX_REPLICAS);
+  if (num_times < 1 || num_samples < 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_times = %d, num_samples = %d (both >= 1)",
+                num_times, num_samples);
+  if (num_quantiles < 1 || num_quantiles > DDD_ROLLOUT_MAX_QUANTILES)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_quantiles = %d out of range [1, %d]",
+                num_quantiles, DDD_ROLLOUT_MAX_QUANTILES);
+  // (one group of lanes per row, at least four rows per workgroup)
+  if ((size_t)replicas * num_times * num_samples > 0x7fffffffu)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "replicas num_times num_samples = %zu: too many rows for one launch",
+                (size_t)replicas * num_times * num_samples);
+  return DDD_OK;
+}
+
+}  // namespace
+
+size_t ddd_rollout_scores_workspace_bytes(int replicas, int num_times, int num_samples,
+                                          int num_quantiles) {
+  if (rollout_sizes(replicas, num_times, num_samples, num_quantiles)) return 0;
+  return ddd::rollout::workspace_bytes(replicas, num_times, num_samples, num_quantiles);
+}
+
+int ddd_rollout_scores(const ddd_rollout_scores_args* a, void* stream) {
+  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
+  if (a->struct_size != (int32_t)sizeof(ddd_rollout_scores_args))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_rollout_scores_args.struct_size = %d, library expects %d (ABI mismatch)",
+                a->struct_size, (int)sizeof(ddd_rollout_scores_args));
+  int rc = rollout_sizes(a->replicas, a->num_times, a->num_samples, a->num_quantiles);
+  if (rc) return rc;
+  if (a->num_points < 1 || a->num_points > DDD_ROLLOUT_MAX_POINTS)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_points = %d out of range [1, %d]", a->num_points,
+                DDD_ROLLOUT_MAX_POINTS);
+  if (a->num_stop_times < 1 || a->num_stop_times > DDD_ROLLOUT_MAX_STOP_TIMES)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_stop_times = %d out of range [1, %d]",
+                a->num_stop_times, DDD_ROLLOUT_MAX_STOP_TIMES);
+  if (a->dtype != DDD_ROLLOUT_F64 && a->dtype != DDD_ROLLOUT_F32)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "dtype = %d (DDD_ROLLOUT_F64 or DDD_ROLLOUT_F32)",
+                a->dtype);
+  if (!a->y_model || !a->exact_low || !a->mae || !a->survival)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "y_model, exact_low, mae and survival must not be NULL");
+  if (!a->times || !a->max_error || !a->frac_good || !a->stop_times)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "times, max_error, frac_good and stop_times must not be NULL");
+  for (int t = 0; t < a->num_times; ++t)
+    if (!std::isfinite(a->times[t]) || (t > 0 && !(a->times[t] > a->times[t - 1])))
+      return fail(DDD_ERR_INVALID_ARGUMENT, "times must be finite and strictly increasing");
+  const size_t ws = ddd::rollout::workspace_bytes(a->replicas, a->num_times, a->num_samples,
+                                                  a->num_quantiles);
+  if (a->workspace == nullptr || a->workspace_bytes < ws)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "workspace of %zu bytes given, ddd_rollout_scores_workspace_bytes = %zu",
+                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws);
+  ddd::rollout::ScoreParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.y_model = a->y_model;
+  p.exact_low = a->exact_low;
+  p.f32 = a->dtype == DDD_ROLLOUT_F32;
+  p.R = a->replicas;
+  p.T = a->num_times;
+  p.S = a->num_samples;
+  p.N = a->num_points;
+  p.Q = a->num_quantiles;
+  p.K = a->num_stop_times;
+  for (int q = 0; q < p.Q; ++q) {
+    p.max_error[q] = a->max_error[q];
+    p.frac_good[q] = a->frac_good[q];
+  }
+  for (int k = 0; k < p.K; ++k) {   // (the times increase: the rows kept are a prefix)
+    int kept = 0;
+    while (kept < p.T && a->times[kept] <= a->stop_times[k]) ++kept;
+    p.kept[k] = kept;
+  }
+  char* base = static_cast<char*>(a->workspace);
+  p.row_abs_sum = a->row_abs_sum != nullptr ? a->row_abs_sum : reinterpret_cast<double*>(base);
+  base += ddd::rollout::row_sum_bytes(p.R, p.T, p.S);
+  p.good = a->good != nullptr ? a->good : reinterpret_cast<uint8_t*>(base);
+  base += ddd::rollout::good_bytes(p.R, p.T, p.S, p.Q);
+  p.times = reinterpret_cast<double*>(base);
+  p.mae = a->mae;
+  p.survival = a->survival;
+  DDD_HIP(ddd::rollout::launch_scores(p, a->times, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }
 

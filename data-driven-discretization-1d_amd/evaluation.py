@@ -21,11 +21,20 @@ sharded and gathered (``distributed``), the analogue of
 
 Arrays are plain NumPy: ``y_model`` [sample, time, x_low], ``y_exact``
 [sample, time, x_high], ``times`` [time].
+
+``evaluate_population`` scores R models at once without the trajectories leaving
+the device: a ``RolloutReference`` prepares what does not depend on the model
+once (the block-averaged exact solution, the error thresholds, the initial
+conditions), ``run_integrate_population`` enqueues the R rollouts side by side
+into one slab and ``ddd_rollout_scores`` scores them in two launches; one small
+host read returns ``mae`` [replica, time_max, sample] and ``survival`` [replica,
+quantile, sample].
 """
 from typing import Dict, Optional, Sequence
 
 import numpy as np
 
+from . import _lib
 from . import distributed
 from . import duckarray
 from . import equations as equations_lib
@@ -204,6 +213,188 @@ def evaluate(model: model_lib.LearnedStencilModel, hparams, y_exact: np.ndarray,
       for q in quantiles])
   return dict(samples=samples, mae=mae, stop_times=np.asarray(stop_times),
               survival=survival, quantiles=np.asarray(quantiles))
+
+
+# ---------------------------------------------------------------------------
+# populations of models, scored on the device
+# ---------------------------------------------------------------------------
+def max_error_thresholds(y_exact, quantiles: Sequence[float]) -> np.ndarray:
+  """``np.quantile(np.abs(y_exact), 1 - quantile)`` for every quantile from ONE sort
+  (mostly_good_survival sorts the full-resolution data once per quantile and model).
+
+  ``y_exact`` is a torch tensor, on the device or not, or anything
+  ``torch.as_tensor`` takes.  Per quantile the two order statistics around
+  ``(n - 1) (1 - quantile)`` are read and interpolated on the host as NumPy's
+  'linear' method does, in the data's own precision, so the values are equal to
+  ``np.quantile``'s, not merely close.  NaNs raise ValueError.
+  """
+  import torch
+  tensor = y_exact if isinstance(y_exact, torch.Tensor) else torch.as_tensor(np.asarray(y_exact))
+  if not tensor.is_floating_point():
+    tensor = tensor.to(torch.float64)
+  ordered, _ = torch.sort(tensor.detach().abs().reshape(-1))
+  n = int(ordered.numel())
+  if n == 0:
+    raise ValueError('y_exact is empty')
+  scalar = np.dtype(str(tensor.dtype).replace('torch.', '')).type
+  picks = []
+  for quantile in quantiles:
+    virtual = (n - 1) * scalar(1 - quantile)
+    lo = min(max(int(np.floor(virtual)), 0), n - 1)
+    picks.append((lo, min(lo + 1, n - 1), scalar(virtual - scalar(np.floor(virtual)))))
+  index = torch.tensor([i for lo, hi, _ in picks for i in (lo, hi)] + [n - 1],
+                       dtype=torch.int64, device=ordered.device)
+  values = ordered[index].cpu().numpy()   # (the only host read; NaNs sort last)
+  if np.isnan(values[-1]):
+    raise ValueError('y_exact cannot have NaNs')
+  out = []
+  for i, (_, _, t) in enumerate(picks):
+    a, b = values[2 * i], values[2 * i + 1]
+    diff = b - a
+    out.append(float(a + diff * t if t < 0.5 else b - diff * (1 - t)))
+  return np.asarray(out, dtype=np.float64)
+
+
+class RolloutReference(object):
+  """What scoring rollouts needs of the exact data and does not depend on the model,
+  prepared once and kept on the device: ``exact_low`` [time, sample, x_low]
+  (analysis.unify_x_coords, bit for bit, in the integrators' layout), ``y0`` =
+  ``exact_low[0]`` (load_initial_conditions), ``max_error`` per quantile.  Reusable
+  across calls and replicas."""
+
+  def __init__(self, y_exact, times, resample_factor: int,
+               quantiles: Sequence[float] = (0.8, 0.9, 0.95),
+               stop_times: Sequence[float] = (5, 10, 20, 40)):
+    torch = _lib.require_gpu()
+    raw = _lib.as_device(y_exact)   # the one upload
+    if raw.dim() != 3:
+      raise ValueError('y_exact must be [sample, time, x_high]')
+    self.times = np.asarray(times, dtype=np.float64)
+    if self.times.shape != (int(raw.shape[1]),):
+      raise ValueError('times must have one entry per time of y_exact')
+    if int(raw.shape[2]) % int(resample_factor):
+      raise ValueError('resample_factor must divide the size of y_exact')
+    self.resample_factor = int(resample_factor)
+    self.quantiles = np.asarray(quantiles, dtype=np.float64)
+    self.stop_times = np.asarray(stop_times)
+    # (in the precision of the data given, as evaluate's np.quantile)
+    self.max_error = max_error_thresholds(raw, [float(q) for q in quantiles])
+    self.y_exact = raw.to(torch.float64)
+    self.exact_low = _lib.rollout_reference(self.y_exact,
+                                            int(raw.shape[2]) // self.resample_factor)
+    self.y0 = self.exact_low[0]
+
+  @property
+  def num_samples(self) -> int:
+    return int(self.exact_low.shape[1])
+
+
+def run_integrate_population(models: Sequence[model_lib.LearnedStencilModel], hparams, y0,
+                             times: np.ndarray, warmup: float = 0, max_step: float = 0.01,
+                             scheme: str = 'bs3', adaptive: Optional[bool] = None,
+                             first_seed: int = 0, streams: int = 4):
+  """run_integrate_batch for R models of one equation at once, everything staying on the
+  device: returns ``(y [replica, time, sample, x], nfev [replica, sample], status
+  [replica, sample])`` as device tensors, replica r's part being what ``models[r]``
+  alone computes from ``y0`` (float64 with the adaptive integrator; float32 with the
+  fixed step, where row 0 is ``y0``).
+
+  The replicas are enqueued round-robin on ``min(R, streams)`` side streams that start
+  behind the current stream and that the current stream then waits for; nothing waits on
+  the host.  Single rank only: sharding stays with ``evaluate``.
+  """
+  torch = _lib.require_gpu()
+  lib = _lib.load_library()
+  if distributed.world_info()[2] > 1:
+    raise RuntimeError('run_integrate_population runs on a single rank; shard with evaluate')
+  models = list(models)
+  if not models or len(set(id(m) for m in models)) != len(models):
+    raise ValueError('models must be a non-empty sequence of distinct models')
+  if int(streams) < 1:
+    raise ValueError('streams must be at least 1')
+  times = np.asarray(times, dtype=np.float64)
+  if adaptive is None:
+    adaptive = scheme == 'bs3'
+  dtype = torch.float64 if adaptive else torch.float32
+  y0 = _lib.as_device(y0, dtype)
+  if y0.dim() != 2 or any(int(y0.shape[1]) != m.num_points for m in models):
+    raise ValueError('y0 must be [sample, x] on the grid of every model')
+  samples, points = int(y0.shape[0]), int(y0.shape[1])
+  if not adaptive:
+    spacing = np.diff(times)
+    if len(times) < 2 or not np.allclose(spacing, spacing[0]):
+      raise ValueError('times must be uniformly spaced')
+    save_every = int(round(spacing[0] / max_step))
+    if (save_every < 1 or
+        abs(save_every * max_step - spacing[0]) > 1e-9 * max(1, spacing[0])):
+      raise ValueError('output spacing {} is not a multiple of dt {}'
+                       .format(spacing[0], max_step))
+    num_steps = save_every * (len(times) - 1)
+  if models[0].equation.has_time_dependent_forcing:
+    eqs = [equations_lib.from_hparams(hparams, random_seed=s)[1]
+           for s in range(first_seed, first_seed + samples)]
+    forcing = model_lib.forcing_from_equations(eqs)
+    for model in models:
+      model.set_forcing(forcing)
+  for model in models:
+    model._handle   # pylint: disable=pointless-statement,protected-access  (created here)
+  # every buffer exists before the fork and is returned, so it outlives the join
+  shape = (len(models), len(times), samples, points)
+  y = torch.empty(shape, dtype=dtype, device=y0.device)
+  nfev = torch.zeros((len(models), samples), dtype=torch.int32, device=y0.device)
+  status = torch.zeros((len(models), samples), dtype=torch.int32, device=y0.device)
+  if not adaptive:
+    y[:, 0] = y0
+    nfev.fill_(lib.ddd_scheme_stages(_lib.SCHEMES[scheme]) * num_steps)
+  current = torch.cuda.current_stream()
+  side = [torch.cuda.Stream() for _ in range(min(len(models), int(streams)))]
+  for stream in side:
+    stream.wait_stream(current)
+  for r, model in enumerate(models):
+    with torch.cuda.stream(side[r % len(side)]):
+      if adaptive:
+        model.integrate_adaptive(y0, warmup + times, max_step=max_step,
+                                 out=(y[r], nfev[r], status[r]))
+      else:
+        model.integrate_fixed(y0, num_steps, dt=max_step, t0=float((warmup + times)[0]),
+                              scheme=scheme, save_every=save_every, out=y[r, 1:])
+  for stream in side:
+    current.wait_stream(stream)
+  return y, nfev, status
+
+
+def evaluate_population(models: Sequence[model_lib.LearnedStencilModel], hparams,
+                        reference: RolloutReference, keep_trajectories: bool = False,
+                        **kwargs):
+  """``evaluate`` for R models at once (run_evaluation.py:181-216 per model): the
+  rollouts of ``run_integrate_population`` (``kwargs``) from ``reference.y0``, scored by
+  ``ddd_rollout_scores`` against ``reference``, then one host read.
+
+  Returns dict(mae [replica, time_max, sample], survival [replica, quantile, sample],
+  num_evals [replica, sample], status [replica, sample], stop_times, quantiles) and,
+  with ``keep_trajectories``, samples = dict(y [replica, sample, time, x], time, x,
+  sample).
+  """
+  torch = _lib.require_gpu()
+  time = kwargs.get('warmup', 0) + reference.times
+  y, nfev, status = run_integrate_population(models, hparams, reference.y0, reference.times,
+                                             **kwargs)
+  mae, survival = _lib.rollout_scores(y, reference.exact_low, time, reference.max_error,
+                                      reference.quantiles, reference.stop_times)
+  parts = (mae, survival, nfev, status)   # (int32 is exact in float64)
+  host = torch.cat([part.reshape(-1).to(torch.float64) for part in parts]).cpu().numpy()
+  mae, survival, nfev, status = (
+      chunk.reshape(tuple(part.shape)) for chunk, part in
+      zip(np.split(host, np.cumsum([part.numel() for part in parts])[:-1]), parts))
+  out = dict(mae=mae, survival=survival, num_evals=nfev.astype(np.int64),
+             status=status.astype(np.int32), stop_times=np.asarray(reference.stop_times),
+             quantiles=np.asarray(reference.quantiles))
+  if keep_trajectories:
+    out['samples'] = dict(
+        y=y.permute(0, 2, 1, 3).contiguous().cpu().numpy(), time=time,
+        x=models[0].equation.grid.solution_x,
+        sample=kwargs.get('first_seed', 0) + np.arange(reference.num_samples))
+  return out
 
 
 def _data(ds, name):

@@ -361,7 +361,7 @@ class _DeviceModel(object):
 
 
   def integrate_adaptive(self, y0, times, rtol: float = 1e-3, atol: float = 1e-6,
-                         max_step: float = 0.01, max_attempts: int = 0):
+                         max_step: float = 0.01, max_attempts: int = 0, out=None):
     """SciPy RK23 with one step-size controller per sample, on the device.
 
     The batched form of ``integrate.odeint`` (integrate.py:143-169): every
@@ -370,7 +370,9 @@ class _DeviceModel(object):
     max_step=max_step, method='RK23')`` would, in one launch.  Returns
     ``(y [time, batch, x] float64, nfev [batch] int32, status [batch] int32)``
     as device tensors; status 0 = finished, -1 = step size too small (the
-    sample's remaining rows are NaN), -2 = attempt limit.
+    sample's remaining rows are NaN), -2 = attempt limit.  ``out``: the caller's
+    contiguous ``(y, nfev, status)`` device tensors of those shapes and types (nfev and
+    status zeroed) to write into instead of allocating; they are returned.
     """
     lib = _lib.load_library()
     torch, y0 = self._check_state(y0, _lib._torch().float64)
@@ -378,10 +380,20 @@ class _DeviceModel(object):
     if times.ndim != 1 or times.size < 1:
       raise ValueError('times must be a non-empty 1-D array')
     batch = y0.shape[0]
-    out = torch.empty((times.size,) + tuple(y0.shape), dtype=torch.float64,
-                      device=y0.device)
-    nfev = torch.zeros(batch, dtype=torch.int32, device=y0.device)
-    status = torch.zeros(batch, dtype=torch.int32, device=y0.device)
+    if out is None:
+      out = torch.empty((times.size,) + tuple(y0.shape), dtype=torch.float64,
+                        device=y0.device)
+      nfev = torch.zeros(batch, dtype=torch.int32, device=y0.device)
+      status = torch.zeros(batch, dtype=torch.int32, device=y0.device)
+    else:
+      out, nfev, status = out
+      for tensor, dtype, shape in ((out, torch.float64, (times.size,) + tuple(y0.shape)),
+                                   (nfev, torch.int32, (batch,)),
+                                   (status, torch.int32, (batch,))):
+        if (tuple(tensor.shape) != shape or tensor.dtype != dtype or not tensor.is_cuda or
+            not tensor.is_contiguous()):
+          raise ValueError('out must be contiguous device tensors (y {} float64, nfev and '
+                           'status [{}] int32)'.format((times.size,) + tuple(y0.shape), batch))
     _lib.check(lib.ddd_integrate_adaptive_f64(
         self._handle, times.ctypes.data_as(_lib._D), int(times.size),
         float(rtol), float(atol), float(max_step), int(max_attempts),

@@ -550,21 +550,38 @@ class Inferer(object):
 def select_replica(rows, key: str):
   """(replica, value) of the best replica at the last evaluation: the smallest last-row
   value of `key` ('loss' or a metric key such as 'test_mae/u_t'), the largest for a
-  'frac_below_baseline' key; NaN never wins; ties go to the lowest index."""
+  'frac_below_baseline' or a 'survival' key (rollout_metrics); NaN never wins; ties go to
+  the lowest index."""
   values = []
   for replica_rows in rows:
     if key not in replica_rows[-1]:
       raise KeyError('select = {!r}: the rows have {}'.format(key, sorted(replica_rows[-1])))
     values.append(float(replica_rows[-1][key]))
-  sign = -1.0 if 'frac_below_baseline' in key else 1.0
+  sign = -1.0 if 'frac_below_baseline' in key or 'survival' in key else 1.0
   ranked = [sign * v if np.isfinite(v) else np.inf for v in values]
   best = int(np.argmin(ranked))
   return best, values[best]
 
 
+def rollout_metrics(result) -> List[Dict[str, float]]:
+  """One dict per replica from evaluation.evaluate_population's result: the means over the
+  samples, 'rollout_mae/<stop time>' (smaller is better) and 'rollout_survival/<quantile>'
+  (larger is better; select_replica knows).  A NaN sample makes its mean NaN."""
+  mae, survival = np.asarray(result['mae']), np.asarray(result['survival'])
+  rows = []
+  for r in range(mae.shape[0]):
+    row = {'rollout_mae/{:g}'.format(float(stop)): float(np.mean(mae[r, k]))
+           for k, stop in enumerate(result['stop_times'])}
+    row.update({'rollout_survival/{:g}'.format(float(q)): float(np.mean(survival[r, i]))
+                for i, q in enumerate(result['quantiles'])})
+    rows.append(row)
+  return rows
+
+
 def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], hparams,
                         init_seeds: Sequence[int], learning_rates=None, seed: int = 0,
-                        num_steps: int = None, metrics: bool = False, select: str = None):
+                        num_steps: int = None, metrics: bool = False, select: str = None,
+                        rollout=None):
   """training_loop(..., seed=seed, fused=True) for R replicas at once: the same dataset,
   train / validation split and minibatch order; replica r starts from
   LearnedStencilModel(coarse, hparams, init_seed=init_seeds[r]) and follows
@@ -578,7 +595,11 @@ def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], h
   with metrics_one_linear.  select: 'loss' or, with metrics, any key of the rows such as
   'test_mae/u_t': returns (rows, best) with best the index of the best replica at the last
   evaluation (select_replica), and writes best.json {'replica', 'key', 'value',
-  'checkpoint_dir'} next to the checkpoint directories."""
+  'checkpoint_dir'} next to the checkpoint directories.
+
+  rollout: an evaluation.RolloutReference; the exported models are then rolled out once
+  after the last stretch (evaluation.evaluate_population) and the keys of rollout_metrics
+  are added to every replica's last row, where select can name them."""
   if len(checkpoint_dirs) != len(init_seeds):
     raise ValueError('one checkpoint directory per init seed')
   hparams = copy.deepcopy(hparams)
@@ -631,8 +652,14 @@ def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], h
     step = stop
     if step % hparams.eval_interval == 0:
       evaluate(step)
-  for model, checkpoint_dir in zip(trainer.export(), checkpoint_dirs):
+  exported = trainer.export()
+  for model, checkpoint_dir in zip(exported, checkpoint_dirs):
     model.save(checkpoint_dir)
+  if rollout is not None:
+    from . import evaluation   # (evaluation does not import training)
+    scores = rollout_metrics(evaluation.evaluate_population(exported, hparams, rollout))
+    for replica_rows, row in zip(rows, scores):
+      replica_rows[-1].update(row)
   if select is None:
     return rows
   best, value = select_replica(rows, select)

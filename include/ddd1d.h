@@ -739,6 +739,87 @@ DDD_API size_t ddd_eval_metrics_workspace_bytes(const ddd_config* cfg, int rows_
 DDD_API int ddd_eval_metrics(const ddd_config* cfg, const ddd_eval_metrics_args* args,
                              void* stream);
 
+/* ---- rollout scores on the device -------------------------------------------
+ * Replaces: the scoring of scripts/run_evaluation.py:181-216 over analysis.py:39-90
+ * (unify_x_coords, is_good, mostly_good, calculate_survival, mostly_good_survival
+ * and the mean absolute error up to each stop time), which the reference runs on
+ * the host per model over whole [sample, time, x] trajectories.  Here the exact
+ * data is block-averaged once on the device (ddd_rollout_reference) and the
+ * trajectories of R replicas, as the integrators wrote them, are scored where they
+ * are (ddd_rollout_scores: two launches whatever R is).  Stateless: no model
+ * handle, no ddd_config. */
+#define DDD_ROLLOUT_MAX_QUANTILES 8
+#define DDD_ROLLOUT_MAX_STOP_TIMES 16
+#define DDD_ROLLOUT_MAX_POINTS 1024
+#define DDD_ROLLOUT_MAX_FACTOR 128
+#define DDD_ROLLOUT_F64 0 /* y_model is float64 (the adaptive integrator's output) */
+#define DDD_ROLLOUT_F32 1 /* y_model is float32 (the fixed-step integrator's) */
+
+typedef struct ddd_rollout_reference_args {
+  int32_t struct_size;   /* = sizeof(ddd_rollout_reference_args), checked */
+  int32_t num_samples;   /* S >= 1 */
+  int32_t num_times;     /* T >= 1 */
+  int32_t num_points_exact; /* X = f N, 1 <= f <= DDD_ROLLOUT_MAX_FACTOR */
+  int32_t num_points;    /* N in [1, DDD_ROLLOUT_MAX_POINTS] */
+  const double* y_exact; /* device [S][T][X] */
+  double* exact_low;     /* out, device [T][S][N] (the layout of the trajectories) */
+} ddd_rollout_reference_args;
+
+/* exact_low[t][s][j] = mean of y_exact[s][t][j f .. j f + f - 1], added in the order
+ * numpy.mean uses on a contiguous last axis (below eight values left to right; else
+ * eight accumulators over the full groups of eight, combined as a balanced tree, then
+ * the remaining f mod 8 values left to right; one division by f): bit for bit
+ * analysis.unify_x_coords, and row t = 0 is run_evaluation.py's
+ * load_initial_conditions.  One launch, enqueued on `stream`: no synchronisation, no
+ * copy to the host, no graph capture.  Arguments are checked before any device work. */
+DDD_API int ddd_rollout_reference(const ddd_rollout_reference_args* args, void* stream);
+
+/* With e = |y_model - exact_low| in float64 (a float32 y_model converted first):
+ *   row_abs_sum[r][t][s] = sum over x of e
+ *   good[r][q][t][s]     = ((double)#{x : e <= max_error[q]} / (double)N) >= frac_good[q]
+ *                          (is_good(...).mean(-1) >= frac_good; a NaN point is not good)
+ *   survival[r][q][s]    = times[first t with good == 0], times[T-1] if there is none
+ *   mae[r][k][s]         = (sum of row_abs_sum over the t with times[t] <= stop_times[k],
+ *                          in time order) / (their number N); NaN if a row kept is NaN
+ *                          or none is kept
+ * Each row is summed in an order that depends on N alone and there are no atomics:
+ * equal inputs give equal bits, and replica r of a call equals the call on replica r
+ * alone. */
+typedef struct ddd_rollout_scores_args {
+  int32_t struct_size;   /* = sizeof(ddd_rollout_scores_args), checked */
+  int32_t replicas;      /* R in [1, DDD_MAX_REPLICAS] */
+  int32_t num_times;     /* T >= 1 */
+  int32_t num_samples;   /* S >= 1 */
+  int32_t num_points;    /* N in [1, DDD_ROLLOUT_MAX_POINTS] */
+  int32_t num_quantiles; /* Q in [1, DDD_ROLLOUT_MAX_QUANTILES] */
+  int32_t num_stop_times; /* K in [1, DDD_ROLLOUT_MAX_STOP_TIMES] */
+  int32_t dtype;         /* DDD_ROLLOUT_F64 or DDD_ROLLOUT_F32: the type of y_model */
+  const void* y_model;   /* device [R][T][S][N] */
+  const double* exact_low; /* device [T][S][N] */
+  const double* times;   /* HOST [T], finite and strictly increasing */
+  const double* max_error; /* HOST [Q] */
+  const double* frac_good; /* HOST [Q] */
+  const double* stop_times; /* HOST [K] */
+  double* mae;           /* out, device [R][K][S] */
+  double* survival;      /* out, device [R][Q][S] */
+  double* row_abs_sum;   /* out, device [R][T][S], or NULL */
+  uint8_t* good;         /* out, device [R][Q][T][S], or NULL */
+  void* workspace;       /* ddd_rollout_scores_workspace_bytes(R, T, S, Q) bytes, device,
+                            8-byte aligned */
+  size_t workspace_bytes;
+} ddd_rollout_scores_args;
+
+/* Bytes of the caller-allocated workspace of ddd_rollout_scores (the row sums, the
+ * good flags and the times); 0 on error, replicas outside [1, DDD_MAX_REPLICAS]
+ * included. */
+DDD_API size_t ddd_rollout_scores_workspace_bytes(int replicas, int num_times, int num_samples,
+                                                  int num_quantiles);
+/* Enqueues a copy of `times` (through a page-locked buffer of the library's: the
+ * caller's arrays are free on return) and the two launches: no stream synchronisation,
+ * no copy to the host, no graph capture.  Arguments are checked before any device
+ * work. */
+DDD_API int ddd_rollout_scores(const ddd_rollout_scores_args* args, void* stream);
+
 /* ---- differentiable evaluation --------------------------------------------
  * Replaces: tf.gradients through model.predict_result (model.py:664-697), the
  * building block of the reference's differentiable time integration

@@ -1,0 +1,154 @@
+"""Rollout evaluations of a replica population on one GPU, printed as one JSON object:
+evaluation.evaluate_population over R models (R adaptive rollouts side by side into one slab,
+ddd_rollout_scores in two launches, one host read) against the route before it existed: R
+sequential evaluation.evaluate calls (one adaptive launch each, the whole trajectory copied to
+the host, NumPy scores with np.quantile per quantile and model).
+
+Default Burgers net (5 taps x 32 filters, 3 layers) at N = 32, 100 samples, rollouts to
+t = 10 at 101 output times, R in {1, 4, 16}, replica r from init seed r.  The "exact" data
+is replica 0's own trajectory repeated 4 times along x plus seeded noise (scoring does not
+care where exact data comes from).  Per R and per version a child process of its own, the
+versions alternated over `rounds` (at least 3) rounds:
+  a  R x evaluation.evaluate
+  b  evaluate_population(streams=1)
+  c  evaluate_population(streams=4)
+  s  scoring alone, on trajectories resident on the device: NumPy after a host copy
+     against the two launches and their host read
+Every timing starts behind a device synchronise and ends behind one, by wall clock; the
+RolloutReference is built before the clock starts (it does not depend on the models).
+Medians and the spread (max - min) / median over the rounds are reported.
+
+  python profiles/tools/rollout_population_throughput.py [--rounds 3]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+REPLICAS = [1, 4, 16]
+NUM_POINTS, SAMPLES, FACTOR = 32, 100, 4
+TIMES = np.linspace(0.0, 10.0, 101)
+QUANTILES, STOP_TIMES = (0.8, 0.9, 0.95), (5, 10, 20, 40)
+
+
+def _setup(replicas):
+  import ddd1d_amd
+  from ddd1d_amd import equations, evaluation, model as model_lib
+  ddd1d_amd._lib.load_library()
+  hp = ddd1d_amd.create_hparams(
+      'burgers', conservative=True, resample_factor=FACTOR,
+      equation_kwargs=json.dumps({'num_points': FACTOR * NUM_POINTS}))
+  _, eq = equations.from_hparams(hp)
+  models = [model_lib.LearnedStencilModel(eq, hp, init_seed=r) for r in range(replicas)]
+  params = model_lib.batched_forcing_parameters(range(1000, 1000 + SAMPLES), nparams=10)
+  x = eq.grid.solution_x
+  y0 = 0.3 * np.sum(params['a'][..., None] * np.sin(
+      2 * np.pi * params['k'][..., None] * x / eq.grid.period + params['phi'][..., None]), axis=1)
+  own = evaluation.run_integrate_batch(models[0], hp, y0, TIMES)['y']
+  own = np.nan_to_num(own)   # (exact data must not hold NaNs)
+  noise = 0.02 * np.random.RandomState(0).standard_normal(own.shape[:2] + (FACTOR * NUM_POINTS,))
+  return hp, models, np.repeat(own, FACTOR, axis=-1) + noise
+
+
+def measure(version, replicas, repeats):
+  import torch
+  from ddd1d_amd import _lib, evaluation
+  hp, models, y_exact = _setup(replicas)
+  reference = evaluation.RolloutReference(y_exact, TIMES, FACTOR, quantiles=QUANTILES,
+                                          stop_times=STOP_TIMES)
+
+  def evaluate_each():
+    return [evaluation.evaluate(model, hp, y_exact, TIMES, stop_times=STOP_TIMES,
+                                quantiles=QUANTILES) for model in models]
+
+  if version == 'a':
+    call = evaluate_each
+  elif version in ('b', 'c'):
+    streams = 1 if version == 'b' else 4
+    call = lambda: evaluation.evaluate_population(models, hp, reference, streams=streams)
+  else:   # scoring alone: trajectories resident, (NumPy after a copy, the two launches)
+    y, _, _ = evaluation.run_integrate_population(models, hp, reference.y0, TIMES)
+    torch.cuda.synchronize()
+
+    def numpy_scores():
+      host = y.permute(0, 2, 1, 3).contiguous().cpu().numpy()
+      out = []
+      for r in range(replicas):
+        named = {'y_model': host[r]}
+        out.append((evaluation.mean_absolute_error(named, y_exact, TIMES, STOP_TIMES),
+                    [evaluation.mostly_good_survival(named, y_exact, TIMES, q)
+                     for q in QUANTILES]))
+      return out
+
+    def device_scores():
+      mae, survival = _lib.rollout_scores(y, reference.exact_low, TIMES, reference.max_error,
+                                          reference.quantiles, reference.stop_times)
+      return mae.cpu().numpy(), survival.cpu().numpy()
+
+    call = None
+  timings = {}
+  for name, fn in ((('call', call),) if call is not None else
+                   (('numpy', numpy_scores), ('device', device_scores))):
+    fn()   # warm-up
+    rows = []
+    for _ in range(repeats):
+      torch.cuda.synchronize()
+      started = time.perf_counter()
+      fn()
+      torch.cuda.synchronize()
+      rows.append(time.perf_counter() - started)
+    timings[name] = rows
+  return {'version': version, 'replicas': replicas, 'seconds': timings}
+
+
+def main():
+  parser = argparse.ArgumentParser()
+  parser.add_argument('--rounds', type=int, default=3)
+  parser.add_argument('--repeats', type=int, default=3, help='timed calls per child process')
+  parser.add_argument('--replicas', type=int, nargs='*', default=REPLICAS)
+  parser.add_argument('--version', default=None, help='one version in this process (the children)')
+  args = parser.parse_args()
+  if args.version is not None:
+    print(json.dumps(measure(args.version, args.replicas[0], args.repeats)))
+    return
+  import torch
+  if not torch.cuda.is_available():
+    raise SystemExit('rollout_population_throughput.py needs a GPU')
+  device = torch.cuda.get_device_name(0)
+  started = time.time()
+  rows = []
+  for replicas in args.replicas:
+    seconds = {}
+    for _ in range(max(args.rounds, 3)):
+      for version in ('a', 'b', 'c', 's'):
+        done = subprocess.run(
+            [sys.executable, os.path.abspath(__file__), '--version', version, '--replicas',
+             str(replicas), '--repeats', str(args.repeats)],
+            capture_output=True, text=True, timeout=600)
+        if done.returncode != 0:   # nothing more is started on the device after a failure
+          raise SystemExit('version {} R = {} failed ({}):\n{}'.format(
+              version, replicas, done.returncode, done.stderr[-2000:]))
+        found = json.loads(done.stdout.strip().splitlines()[-1])['seconds']
+        for name, values in found.items():
+          seconds.setdefault(version + '_' + name, []).extend(values)
+    row = {'replicas': replicas, 'num_points': NUM_POINTS, 'samples': SAMPLES,
+           'times': len(TIMES)}
+    for name, values in seconds.items():
+      median = float(np.median(values))
+      row[name] = {'median_s': median, 'spread': (max(values) - min(values)) / median,
+                   'seconds': values}
+    rows.append(row)
+    print(json.dumps(row), file=sys.stderr, flush=True)
+  print(json.dumps({'tool': 'rollout_population_throughput', 'device': device, 'rows': rows,
+                    'wall_s': time.time() - started}))
+
+
+if __name__ == '__main__':
+  main()
