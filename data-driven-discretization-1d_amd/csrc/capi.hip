@@ -934,12 +934,7 @@ int launch_substep(ddd_model* m, const Plan& p, const ddd::SubstepArgs& a, hipSt
     const long pts = (long)ddd::stream::samples_per_block(m->dp.N) * m->dp.N;
     const long total = (long)a.batch * m->dp.N;
     const unsigned blocks = (unsigned)((total + pts - 1) / pts);
-    if (ddd::stream::quads_for(m->dp.N) == 2)
-      hipLaunchKernelGGL(ddd::stream::fixed_substep_kernel<2>, dim3(blocks),
-                         dim3(ddd::stream::kThreads), 0, stream, m->dp, a);
-    else
-      hipLaunchKernelGGL(ddd::stream::fixed_substep_kernel<1>, dim3(blocks),
-                         dim3(ddd::stream::kThreads), 0, stream, m->dp, a);
+    ddd::stream::launch_fixed_substep(dim3(blocks), stream, m->dp, a);
   } else if (p.route == Route::mfma) {
     const ddd::DevParams dp = launch_params(m, p, sample0);
     const int blocks = group_count(m, p.geo, a.batch);

@@ -278,9 +278,15 @@ __device__ __forceinline__ void weno_minus_plus(const float* u, int pos, int n,
 }
 
 // Godunov flux for u^2/2 (equations.py:341-349).
+// (compare + select, not fminf / fmaxf: minNum / maxNum return the operand that is not NaN,
+// np.minimum / np.maximum -- the reference -- return NaN.  u_minus and u_plus reach differently
+// under WENO, so the flux must be NaN where EITHER is: b is the fall-through of both selects,
+// a NaN in a is passed on by the last one.  Finite operands: the same value, a, b >= +0)
 __device__ __forceinline__ float godunov_flux(float um, float up) {
   const float a = um * um, b = up * up;
-  return 0.5f * (um <= up ? fminf(a, b) : fmaxf(a, b));
+  const float lo = a < b ? a : b, hi = a > b ? a : b;
+  const float pick = um <= up ? lo : hi;
+  return 0.5f * (a != a ? a : pick);
 }
 
 // u_t for the non-flux forms, or the flux for the flux forms.  `d` holds the

@@ -28,11 +28,16 @@ inline bool supports(const DevParams& p) {
          p.G <= kGMax;
 }
 
-template <int kQuads>
+// kG: stencil points, p.G as a compile-time fact.  The loop below stops at kG: the columns
+// g >= G of the zero-padded table multiply points the reference's stencil never touches, and
+// fma(0, NaN, s) = NaN would mark grid points the reference (and fixed_step_kernel, and the
+// lean kernel) leave finite -- integrate.py:161-167 signals divergence by NaN rows.
+template <int kQuads, int kG>
 __global__ __launch_bounds__(kThreads) void fixed_substep_kernel(DevParams p, SubstepArgs a) {
+  static_assert(kG >= 1 && kG <= kGMax, "stencils of 1 to 8 points");
   constexpr int kPer = 4 * kQuads;              // consecutive grid points per thread
   constexpr int kTilePoints = kThreads * kPer;  // grid points per block
-  constexpr int kWin = kPer + 1 + kGMax - 1;    // stencil window of one thread (flux form: +1)
+  constexpr int kWin = kPer + 1 + kG - 1;       // stencil window of one thread (flux form: +1)
   __shared__ float tile[kTilePoints];
   const int n = p.N;
   const int pts = samples_per_block(n) * n;                 // multiple of kPer, <= kTilePoints
@@ -70,7 +75,7 @@ __global__ __launch_bounds__(kThreads) void fixed_substep_kernel(DevParams p, Su
 
   const int s0 = (i0 / n) * n;     // first point of this thread's sample inside the tile
   const int pos0 = i0 - s0;        // its points are pos0 .. pos0 + kPer - 1 (N % kPer == 0)
-  const int gl = p.G >> 1;         // patches[i] = u[(x + i - G/2) mod N]  (model.py:516-533)
+  constexpr int gl = kG >> 1;      // patches[i] = u[(x + i - G/2) mod N]  (model.py:516-533)
   float w[kWin];
 #pragma unroll
   for (int j = 0; j < kWin; ++j) {
@@ -103,7 +108,7 @@ __global__ __launch_bounds__(kThreads) void fixed_substep_kernel(DevParams p, Su
         float s = 0.0f;
         if (d < p.D) {
 #pragma unroll
-          for (int g = 0; g < kGMax; ++g) s = fmaf(p.bias8[d][g], w[q + g], s);
+          for (int g = 0; g < kG; ++g) s = fmaf(p.bias8[d][g], w[q + g], s);
         }
         dv[d] = s;
       }
@@ -299,7 +304,26 @@ __global__ __launch_bounds__(kThreads) void fixed_step_kernel(DevParams p, StepA
   }
 }
 
-// Host side: the instantiation for (equation, stencil width).
+// Host side: the substep kernel's instantiation for (float4 rows per thread, stencil width).
+template <int kQuads>
+inline void launch_fixed_substep_g(int g, dim3 grid, hipStream_t stream, const DevParams& p,
+                                   const SubstepArgs& a) {
+#define DDD_SUBSTEP_G(G) \
+  case G: hipLaunchKernelGGL((fixed_substep_kernel<kQuads, G>), grid, dim3(kThreads), 0, stream, p, a); break;
+  switch (g) {   // (supports: 1 <= G <= 8)
+    DDD_SUBSTEP_G(1) DDD_SUBSTEP_G(2) DDD_SUBSTEP_G(3) DDD_SUBSTEP_G(4) DDD_SUBSTEP_G(5)
+    DDD_SUBSTEP_G(6) DDD_SUBSTEP_G(7)
+    default: hipLaunchKernelGGL((fixed_substep_kernel<kQuads, 8>), grid, dim3(kThreads), 0, stream, p, a); break;
+  }
+#undef DDD_SUBSTEP_G
+}
+inline void launch_fixed_substep(dim3 grid, hipStream_t stream, const DevParams& p,
+                                 const SubstepArgs& a) {
+  if (quads_for(p.N) == 2) launch_fixed_substep_g<2>(p.G, grid, stream, p, a);
+  else launch_fixed_substep_g<1>(p.G, grid, stream, p, a);
+}
+
+// Host side: the step kernel's instantiation for (equation, stencil width).
 template <int kEq>
 inline void launch_fixed_step_eq(int g, dim3 grid, hipStream_t stream, const DevParams& p,
                                  const StepArgs& a, int tiles) {

@@ -58,7 +58,10 @@ static int wrap(int i, int n) {
 
 static float godunov(float um, float up) {
   const float a = um * um, b = up * up;
-  return 0.5f * (um <= up ? fminf(a, b) : fmaxf(a, b));
+  /* np.minimum / np.maximum return NaN where either operand is (fminf / fmaxf do not) */
+  const float lo = a < b ? a : b, hi = a > b ? a : b;
+  const float pick = um <= up ? lo : hi;
+  return 0.5f * (a != a ? a : pick);
 }
 
 /* u_t (plain forms) or the flux (flux forms) from the spatial derivatives. */

@@ -454,6 +454,7 @@ NAN_CASES = [
     ('generic', 'burgers', True, 64, 4, {}),
     ('generic', 'kdv', False, 48, 2, {'kernel_size': 4}),         # even taps: asymmetric reach
     ('auto', 'burgers', True, 64, 4, {'num_layers': 1}),          # lean kernel: no activation at all
+    ('mfma64', 'burgers', True, 64, 4, {'numerical_flux': True}),   # Godunov flux: np.minimum / np.maximum pass NaN
 ]
 
 
