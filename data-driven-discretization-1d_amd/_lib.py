@@ -287,6 +287,9 @@ class DDDError(RuntimeError):
   """A libddd1d call returned a non-zero status."""
 
 
+ERR_UNSUPPORTED = -2   # DDD_ERR_UNSUPPORTED
+
+
 _lib = None
 
 _F = ctypes.POINTER(ctypes.c_float)
@@ -392,6 +395,16 @@ SIGNATURES = {
     'ddd_rollout_scores_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int,
                                                               ctypes.c_int, ctypes.c_int]),
     'ddd_rollout_scores': (ctypes.c_int, [ctypes.POINTER(DDDRolloutScoresArgs), _V]),
+    'ddd_population_create': (ctypes.c_int, [ctypes.POINTER(_V), ctypes.c_int,
+                                             ctypes.POINTER(_V)]),
+    'ddd_population_destroy': (ctypes.c_int, [_V]),
+    'ddd_population_integrate_adaptive_f64': (ctypes.c_int, [_V, _D, ctypes.c_int,
+                                                             ctypes.c_double, ctypes.c_double,
+                                                             ctypes.c_double, ctypes.c_longlong,
+                                                             _V, _V, _V, _V, ctypes.c_int, _V]),
+    'ddd_population_integrate_fixed': (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_double,
+                                                      ctypes.c_double, ctypes.c_int,
+                                                      ctypes.c_int, _V, _V, ctypes.c_int, _V]),
     'ddd_vjp_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(DDDConfig),
                                                    ctypes.c_int]),
     'ddd_result_vjp': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
@@ -440,6 +453,14 @@ def check(status: int):
   if status != 0:
     message = _lib.ddd_last_error().decode('utf-8', 'replace')
     raise DDDError('libddd1d error {}: {}'.format(status, message))
+
+
+def check_supported(status: int):
+  """check(), with DDD_ERR_UNSUPPORTED raised as NotImplementedError (the library's
+  message): for entry points whose callers may choose another route."""
+  if status == ERR_UNSUPPORTED:
+    raise NotImplementedError(_lib.ddd_last_error().decode('utf-8', 'replace'))
+  check(status)
 
 
 def _torch():

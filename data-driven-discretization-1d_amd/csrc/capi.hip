@@ -298,6 +298,9 @@ struct Plan {
   Tile tile = Tile::one_wave;
   bool traced = false;          // (probes) the phase-traced persistent integrator
   const char* name = nullptr;   // ddd_kernel_name; nullptr: no launch recorded
+  // CallFacts::population: why the population form of the planned kernel does not exist
+  // (nullptr: it does -- mfma_population.hip)
+  const char* no_population = nullptr;
 };
 
 }  // namespace
@@ -321,6 +324,7 @@ struct ddd_model {
   float* d_w_input = nullptr;
   float* d_w_hidden = nullptr;
   float* d_w_final4 = nullptr;
+  size_t n_w_input = 0, n_w_hidden = 0, n_w_final4 = 0;   // floats of the three arrays above
   float* d_w_final4_rt = nullptr;
   float* d_w_final4_split = nullptr;
   float* d_w_quad = nullptr;
@@ -495,6 +499,9 @@ int pack_mfma_weights(ddd_model* m, const ddd::pack::NetLayout& net) {
   if (!rc) rc = upload(packed.w_quad, &m->d_w_quad);
   if (!rc) rc = upload(packed.w_final4_half, &m->d_w_final4_half);
   if (!rc) rc = upload(packed.w_t16, &m->d_w_t16);
+  m->n_w_input = packed.w_input.size();
+  m->n_w_hidden = packed.w_hidden.size();
+  m->n_w_final4 = packed.w_final4.size();
   dp.w_input = m->d_w_input;
   dp.w_hidden = m->d_w_hidden;
   dp.w_final4_rt = m->d_w_final4_rt;
@@ -778,6 +785,10 @@ struct CallFacts {
   bool views = false;     // derivative or coefficient views requested
   bool coeffs = false;    // ... coefficients (the WENO kernels write none)
   bool aligned = false;   // every state array 16-byte aligned (the streaming kernels)
+  // a replica population in one launch (ddd_population_*): the machine is filled by
+  // replicas x groups, so none of the small-ensemble geometries; Plan::no_population says
+  // whether the kernel planned has a population form
+  bool population = false;
 };
 
 CallFacts substep_facts(const ddd::SubstepArgs& a) {
@@ -802,7 +813,7 @@ void plan_mfma(const ddd_model* m, const CallFacts& f, Plan* p) {
       if (automatic) eq = spec_equation(m, geo.rows);
       break;
     case Op::persistent:
-      if (geo.rows == 64 && geo.wave_rows == 64 && !f.f64 && automatic &&
+      if (geo.rows == 64 && geo.wave_rows == 64 && !f.f64 && automatic && !f.population &&
           m->dp.w_final4_split != nullptr && spec_equation(m, 64) >= 0) {
         // small ensembles: two 32-row wavefronts per sample (rhs_mfma.h kSplit)
         // measured (profiles/r4_ablation.txt, N = 64): B = 256: 1.63 x the one-wavefront kernel (twice
@@ -837,7 +848,7 @@ void plan_mfma(const ddd_model* m, const CallFacts& f, Plan* p) {
       // on four 16-row wavefronts (rhs_mfma.h kQuad), as for the fixed-step integrators --
       // the reference's callers integrate tens to hundreds of samples
       // (scripts/run_evaluation.py:212-221)
-      const bool want_quad = geo.rows == 64 &&
+      const bool want_quad = geo.rows == 64 && !f.population &&
                              (geo.wave_rows == 16 || (geo.wave_rows == 64 && m->force_rows == 0));
       if (geo.wave_rows != 64) geo = {64, 64};
       eq = spec_equation(m, geo.rows);
@@ -903,6 +914,25 @@ Plan plan_launch(const ddd_model* m, Op op, const CallFacts& f) {
   if (op == Op::step && p.route != Route::stream_fixed && !(p.route == Route::mfma && p.eq >= 0))
     p.op = Op::substep;
   p.name = plan_name(p);
+  if (f.population) {
+    // the population forms built: the per-equation one-wavefront integrators, float32 fixed
+    // step and adaptive (launch.h: integrate_population_spec, adaptive_population_spec)
+    if (!automatic) p.no_population = "an explicit ddd_set_kernel choice";
+    else if (op != Op::persistent && op != Op::adaptive)
+      p.no_population = "only the persistent launch mode and the adaptive integrator";
+    else if (p.route != Route::mfma) p.no_population = "the model is not on the MFMA route";
+    else if (p.geo.rows != 64 || p.geo.wave_rows != 64)
+      p.no_population = "num_points does not divide 64 (four-wavefront 256-row geometry)";
+    else if (p.eq < 0)
+      p.no_population = "no per-equation specialisation (run-time-parameterised, wide or "
+                        "other-tower kernels)";
+    else if (p.tile != Tile::one_wave)
+      p.no_population = "nets of up to 16 filters run on the 16-channel-tile kernels";
+    else if (op == Op::persistent && f.f64) p.no_population = "float64 fixed-step state";
+    // (probe build: the population launches carry neither the phase stamps nor the A/B knobs
+    // that launch_integrate hands the solo kernels)
+    else if (p.traced) p.no_population = "phase tracing is on (probe library)";
+  }
   return p;
 }
 
@@ -2475,14 +2505,13 @@ int ddd_integrate_fixed_f64(ddd_model* m, int scheme, double t0, double dt, int 
                                   static_cast<hipStream_t>(stream));
 }
 
-int ddd_integrate_adaptive_f64(ddd_model* m, const double* times, int n_times, double rtol,
-                               double atol, double max_step, long long max_attempts,
-                               const double* y0, double* y_out, int32_t* nfev,
-                               int32_t* status, int batch, void* stream_) {
-  if (m == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "model is NULL");
-  int rc = chain_close(m);
-  if (rc) return rc;
-  rc = check_batch(m, batch, m->spectral);
+namespace {
+
+// Argument checks of the adaptive entry points (solo and population).
+int check_adaptive_args(const ddd_model* m, const double* times, int n_times, double rtol,
+                        double atol, double max_step, const double* y0, const double* y_out,
+                        const int32_t* nfev, const int32_t* status, int batch) {
+  int rc = check_batch(m, batch, m->spectral);
   if (rc) return rc;
   if (times == nullptr || n_times < 1)
     return fail(DDD_ERR_INVALID_ARGUMENT, "times must hold at least one value");
@@ -2495,13 +2524,14 @@ int ddd_integrate_adaptive_f64(ddd_model* m, const double* times, int n_times, d
     return fail(DDD_ERR_INVALID_ARGUMENT, "rtol and max_step must be positive, atol >= 0");
   if (batch > 0 && (!y0 || !y_out || !nfev || !status))
     return fail(DDD_ERR_INVALID_ARGUMENT, "NULL array");
-  if (m->spectral && is_forced_family(m->cfg.equation))
-    return fail(DDD_ERR_UNSUPPORTED,
-                "the spectral adaptive kernel carries no forcing term: Burgers' forcing(t) "
-                "(equations.py:276-277) would be dropped; integrate it with the host driver "
-                "(integrate.odeint over ddd_time_derivative_f64 + finalize_time_derivative)");
-  if (batch == 0) return DDD_OK;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  return DDD_OK;
+}
+
+// The output times of one adaptive call, on their way to the device through the next slot of
+// the model's page-locked ring (ddd_model::TimeSlot); *out: the slot, whose `dev` the launch
+// reads and whose `done` event the caller records again behind that launch.
+int stage_times(ddd_model* m, const double* times, int n_times, hipStream_t stream,
+                ddd_model::TimeSlot** out) {
   // the caller's array may be gone before the copy runs: upload from a page-locked
   // copy the model owns until the launch that reads it has finished
   ddd_model::TimeSlot& slot = m->time_slot[m->next_time_slot];
@@ -2525,10 +2555,43 @@ int ddd_integrate_adaptive_f64(ddd_model* m, const double* times, int n_times, d
   DDD_HIP(hipMemcpyAsync(slot.dev, slot.host, (size_t)n_times * sizeof(double),
                          hipMemcpyHostToDevice, stream));
   // the slot is busy from HERE on (the copy reads the pinned buffer), whatever happens to
-  // the launch below: an error return between the copy and the launch must not leave a
+  // the launch that follows: an error return between the copy and the launch must not leave a
   // slot that looks free while the copy is still pending
   DDD_HIP(hipEventRecord(slot.done, stream));
   slot.in_flight = true;
+  *out = &slot;
+  return DDD_OK;
+}
+
+// max_attempts <= 0: a thousand times the attempts of a run at max_step
+long long attempt_limit(const double* times, int n_times, double max_step, long long max_attempts) {
+  if (max_attempts > 0) return max_attempts;
+  const double span = times[n_times - 1] - times[0];
+  return (long long)std::min(1e15, std::ceil(span / max_step) * 1000.0 + 100000.0);
+}
+
+}  // namespace
+
+int ddd_integrate_adaptive_f64(ddd_model* m, const double* times, int n_times, double rtol,
+                               double atol, double max_step, long long max_attempts,
+                               const double* y0, double* y_out, int32_t* nfev,
+                               int32_t* status, int batch, void* stream_) {
+  if (m == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "model is NULL");
+  int rc = chain_close(m);
+  if (rc) return rc;
+  rc = check_adaptive_args(m, times, n_times, rtol, atol, max_step, y0, y_out, nfev, status, batch);
+  if (rc) return rc;
+  if (m->spectral && is_forced_family(m->cfg.equation))
+    return fail(DDD_ERR_UNSUPPORTED,
+                "the spectral adaptive kernel carries no forcing term: Burgers' forcing(t) "
+                "(equations.py:276-277) would be dropped; integrate it with the host driver "
+                "(integrate.odeint over ddd_time_derivative_f64 + finalize_time_derivative)");
+  if (batch == 0) return DDD_OK;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  ddd_model::TimeSlot* slot_ptr = nullptr;
+  rc = stage_times(m, times, n_times, stream, &slot_ptr);
+  if (rc) return rc;
+  ddd_model::TimeSlot& slot = *slot_ptr;
   ddd::AdaptiveArgs a{};
   // ... and is free again once the launch enqueued below has run
   const auto enqueued = [&]() -> int {
@@ -2540,12 +2603,7 @@ int ddd_integrate_adaptive_f64(ddd_model* m, const double* times, int n_times, d
   a.times = slot.dev; a.n_times = n_times;
   a.rtol = rtol; a.atol = atol; a.max_step = max_step;
   a.y0 = y0; a.y_out = y_out; a.nfev = nfev; a.status = status; a.batch = batch;
-  if (max_attempts <= 0) {
-    // generous default: a thousand times the attempts of a run at max_step
-    const double span = times[n_times - 1] - times[0];
-    max_attempts = (long long)std::min(1e15, std::ceil(span / max_step) * 1000.0 + 100000.0);
-  }
-  a.max_attempts = max_attempts;
+  a.max_attempts = attempt_limit(times, n_times, max_step, max_attempts);
   const Plan p = plan_launch(m, Op::adaptive, {batch, true});
   m->last_plan = p;
   if (p.route == Route::spectral) {
@@ -2606,6 +2664,209 @@ int ddd_integrate_adaptive_f64(ddd_model* m, const double* times, int n_times, d
     });
   }
   return enqueued();
+}
+
+// ---- replica populations in one launch (mfma_population.hip) ---------------------------
+struct ddd_population {
+  ddd_model* model0 = nullptr;   // everything that is not a weight, at call time (launch_params)
+  int replicas = 0;
+  float* d_w_input = nullptr;    // [R][stride]: the replicas' packed weights, copied at creation
+  float* d_w_hidden = nullptr;
+  float* d_w_final4 = nullptr;
+  ddd::PopulationStrides strides{};   // (the weight strides; the output strides are per call)
+};
+
+namespace {
+
+// Equation, grid, tower, head and scaling of two configurations are the same.  Of
+// derivative_orders[] and input_sizes[] only the num_derivatives entries in use are compared
+// (a C caller may leave the rest unset); reserved[] is not looked at.
+bool same_architecture(const ddd_config& a, const ddd_config& b) {
+  if (a.equation != b.equation || a.num_points != b.num_points ||
+      a.num_derivatives != b.num_derivatives || a.dx != b.dx || a.period != b.period ||
+      a.eta != b.eta || a.standard_deviation != b.standard_deviation ||
+      a.stencil_size != b.stencil_size || a.model_target != b.model_target ||
+      a.num_layers != b.num_layers || a.filter_size != b.filter_size ||
+      a.kernel_size != b.kernel_size || a.activation != b.activation ||
+      a.polynomial_accuracy_order != b.polynomial_accuracy_order ||
+      a.ensure_unbiased_coefficients != b.ensure_unbiased_coefficients ||
+      a.weno_reconstruction != b.weno_reconstruction)
+    return false;
+  for (int d = 0; d < a.num_derivatives && d < DDD_MAX_DERIVATIVES; ++d)
+    if (a.derivative_orders[d] != b.derivative_orders[d] || a.input_sizes[d] != b.input_sizes[d])
+      return false;
+  return true;
+}
+
+// The plan of a population launch on model m, or DDD_ERR_UNSUPPORTED with the reason.
+int plan_population(const ddd_model* m, Op op, int batch, Plan* out, const char* who) {
+  CallFacts f{batch, op == Op::adaptive};
+  f.population = true;
+  *out = plan_launch(m, op, f);
+  if (out->no_population != nullptr)
+    return fail(DDD_ERR_UNSUPPORTED, "%s: no population kernel for this configuration: %s%s%s",
+                who, out->no_population,
+                out->route != Route::mfma && !m->mfma_reason.empty() ? ": " : "",
+                out->route != Route::mfma ? m->mfma_reason.c_str() : "");
+  return DDD_OK;
+}
+
+// replica r's weights in place of model 0's
+ddd::DevParams population_params(ddd_population* pop, const Plan& p) {
+  ddd::DevParams dp = launch_params(pop->model0, p);
+  dp.w_input = pop->d_w_input;
+  dp.w_hidden = pop->d_w_hidden;
+  dp.w_final4 = pop->d_w_final4;
+  return dp;
+}
+
+}  // namespace
+
+int ddd_population_destroy(ddd_population* pop) {
+  if (pop == nullptr) return DDD_OK;
+  free_dev(pop->d_w_input); free_dev(pop->d_w_hidden); free_dev(pop->d_w_final4);
+  delete pop;
+  return DDD_OK;
+}
+
+int ddd_population_create(ddd_model* const* models, int replicas, ddd_population** out) {
+  if (out == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "out is NULL");
+  *out = nullptr;
+  if (models == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "models is NULL");
+  if (replicas < 1 || replicas > DDD_MAX_REPLICAS)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "replicas = %d outside [1, %d]", replicas,
+                DDD_MAX_REPLICAS);
+  for (int r = 0; r < replicas; ++r) {
+    if (models[r] == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "models[%d] is NULL", r);
+    for (int q = 0; q < r; ++q)
+      if (models[q] == models[r])
+        return fail(DDD_ERR_INVALID_ARGUMENT, "models[%d] and models[%d] are the same model", q, r);
+  }
+  const ddd_model* m0 = models[0];
+  for (int r = 1; r < replicas; ++r) {
+    const ddd_model* m = models[r];
+    if (!same_architecture(m->cfg, m0->cfg))
+      return fail(DDD_ERR_UNSUPPORTED,
+                  "models[%d]: ddd_config differs from models[0]'s (replicas share one "
+                  "architecture: equation, grid, tower, head, standard deviation)", r);
+  }
+  for (int r = 0; r < replicas; ++r) {
+    const ddd_model* m = models[r];
+    Plan p;
+    char who[32];
+    snprintf(who, sizeof(who), "models[%d]", r);
+    // (both integrators, whatever forcing the model carries now: the call plans again)
+    int rc = plan_population(m, Op::adaptive, 1, &p, who);
+    if (!rc) rc = plan_population(m, Op::persistent, 1, &p, who);
+    if (rc) return rc;
+    const ddd::DevParams& a = m->dp;
+    const ddd::DevParams& b = m0->dp;
+    if (std::memcmp(a.ns8, b.ns8, sizeof(a.ns8)) != 0 ||
+        std::memcmp(a.bias8, b.bias8, sizeof(a.bias8)) != 0 || a.dsel_bits != b.dsel_bits ||
+        a.dsel_valid != b.dsel_valid || m->spec_folded != m0->spec_folded ||
+        a.fin4_groups != b.fin4_groups || a.exact_div != b.exact_div)
+      return fail(DDD_ERR_UNSUPPORTED,
+                  "models[%d]: projection tables differ from models[0]'s (the replicas' "
+                  "launch reads models[0]'s)", r);
+    if (m->n_w_input != m0->n_w_input || m->n_w_hidden != m0->n_w_hidden ||
+        m->n_w_final4 != m0->n_w_final4 || m->d_w_input == nullptr || m->d_w_hidden == nullptr ||
+        m->d_w_final4 == nullptr)
+      return fail(DDD_ERR_UNSUPPORTED, "models[%d]: packed weight arrays of other sizes than "
+                  "models[0]'s", r);
+  }
+  ddd_population* pop = new ddd_population();
+  pop->model0 = models[0];
+  pop->replicas = replicas;
+  pop->strides.w_input = (long long)m0->n_w_input;
+  pop->strides.w_hidden = (long long)m0->n_w_hidden;
+  pop->strides.w_final4 = (long long)m0->n_w_final4;
+  const auto gather = [&](float** dst, size_t n, float* ddd_model::*src) -> int {
+    DDD_HIP(hipMalloc(reinterpret_cast<void**>(dst), (size_t)replicas * n * sizeof(float)));
+    for (int r = 0; r < replicas; ++r)
+      DDD_HIP(hipMemcpy(*dst + (size_t)r * n, models[r]->*src, n * sizeof(float),
+                        hipMemcpyDeviceToDevice));
+    return DDD_OK;
+  };
+  int rc = gather(&pop->d_w_input, m0->n_w_input, &ddd_model::d_w_input);
+  if (!rc) rc = gather(&pop->d_w_hidden, m0->n_w_hidden, &ddd_model::d_w_hidden);
+  if (!rc) rc = gather(&pop->d_w_final4, m0->n_w_final4, &ddd_model::d_w_final4);
+  if (!rc) DDD_HIP(hipDeviceSynchronize());   // (the copies have read the models' arrays)
+  if (rc) { ddd_population_destroy(pop); return rc; }
+  *out = pop;
+  return DDD_OK;
+}
+
+int ddd_population_integrate_adaptive_f64(ddd_population* pop, const double* times, int n_times,
+                                          double rtol, double atol, double max_step,
+                                          long long max_attempts, const double* y0,
+                                          double* y_out, int32_t* nfev, int32_t* status,
+                                          int batch, void* stream_) {
+  if (pop == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "population is NULL");
+  ddd_model* m = pop->model0;
+  int rc = chain_close(m);
+  if (rc) return rc;
+  rc = check_adaptive_args(m, times, n_times, rtol, atol, max_step, y0, y_out, nfev, status, batch);
+  if (rc) return rc;
+  if (batch == 0) return DDD_OK;
+  Plan p;
+  rc = plan_population(m, Op::adaptive, batch, &p, "models[0]");
+  if (rc) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  ddd_model::TimeSlot* slot = nullptr;
+  rc = stage_times(m, times, n_times, stream, &slot);
+  if (rc) return rc;
+  ddd::AdaptiveArgs a{};
+  a.times = slot->dev; a.n_times = n_times;
+  a.rtol = rtol; a.atol = atol; a.max_step = max_step;
+  a.y0 = y0; a.y_out = y_out; a.nfev = nfev; a.status = status; a.batch = batch;
+  a.max_attempts = attempt_limit(times, n_times, max_step, max_attempts);
+  m->last_plan = p;
+  const ddd::DevParams dp = population_params(pop, p);
+  ddd::PopulationStrides s = pop->strides;
+  s.y_out = (long long)n_times * batch * m->dp.N;
+  s.samples = batch;
+  const int groups = group_count(m, p.geo, batch);
+  with_equation(p.eq, [&](auto eq) {
+    ddd::launch::adaptive_population_spec<decltype(eq)::value>(dp, a, s, groups, pop->replicas,
+                                                               stream);
+  });
+  DDD_HIP(hipGetLastError());
+  DDD_HIP(hipEventRecord(slot->done, stream));   // the slot is free once the launch has run
+  slot->in_flight = true;
+  return DDD_OK;
+}
+
+int ddd_population_integrate_fixed(ddd_population* pop, int scheme, double t0, double dt,
+                                   int n_steps, int save_every, const float* y0, float* y_out,
+                                   int batch, void* stream_) {
+  if (pop == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "population is NULL");
+  ddd_model* m = pop->model0;
+  int rc = chain_close(m);
+  if (rc) return rc;
+  rc = check_integrate_args(m, n_steps, save_every, y0, y_out, batch);
+  if (rc) return rc;
+  ddd::IntegrateArgs a{};
+  rc = make_tableau(scheme, &a.tab);
+  if (rc) return rc;
+  if (batch == 0 || n_steps == 0) return DDD_OK;
+  Plan p;
+  rc = plan_population(m, Op::persistent, batch, &p, "models[0]");
+  if (rc) return rc;
+  a.t0 = t0; a.dt = dt; a.n_steps = n_steps; a.save_every = save_every;
+  a.sc = make_stage_consts(a.tab, dt);
+  a.y0 = y0; a.y_out = y_out; a.batch = batch;
+  m->last_plan = p;
+  const ddd::DevParams dp = population_params(pop, p);
+  ddd::PopulationStrides s = pop->strides;
+  s.y_out = (long long)(n_steps / save_every) * batch * m->dp.N;
+  s.samples = batch;
+  const int groups = group_count(m, p.geo, batch);
+  with_equation(p.eq, [&](auto eq) {
+    ddd::launch::integrate_population_spec<decltype(eq)::value>(
+        dp, a, s, groups, pop->replicas, static_cast<hipStream_t>(stream_));
+  });
+  DDD_HIP(hipGetLastError());
+  return DDD_OK;
 }
 
 int ddd_circulant_apply_f64(const double* kernel, const double* in, double* out, int rows,

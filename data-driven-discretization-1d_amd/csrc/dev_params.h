@@ -148,6 +148,15 @@ struct AdaptiveArgs {
   long long max_attempts;   // safety net against runaway samples (SciPy has none)
 };
 
+// Population launches (mfma_population.hip: replicas on grid.y): what workgroup (g, r) adds,
+// r times, to the pointers of DevParams and of the call's arguments before it runs group g
+// as a solo launch would.  A struct of its own: DevParams is every kernel's argument block.
+struct PopulationStrides {
+  long long w_input, w_hidden, w_final4;   // floats per replica of the packed weight arrays
+  long long y_out;                         // state elements per replica: rows x batch x N
+  long long samples;                       // nfev / status entries per replica: batch
+};
+
 // One whole Runge-Kutta step in one launch (DDD_LAUNCH_PER_STEP; rhs_mfma.h: step_multi_kernel)
 struct StepArgs {
   double t, dt;

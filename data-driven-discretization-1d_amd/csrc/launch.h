@@ -5,6 +5,8 @@
 //                   specialised persistent integrators (float32 state in both
 //                   geometries, float64 state in the one-wave geometry, the
 //                   traced instantiation) and the multi-group substep kernels
+//   mfma_population.hip  once per equation id: the population forms (replicas on grid.y)
+//                   of the one-wavefront float32 and adaptive integrators
 //   mfma_runtime.hip  the run-time-parameterised kernels (kEq = -1), once per
 //                     (geometry, state type)
 //   capi.hip          C ABI, packing, every other kernel
@@ -64,6 +66,17 @@ template <int kEq>
 void adaptive_spec(int rows, const DevParams& p, const AdaptiveArgs& a, int blocks,
                    hipStream_t stream);
 
+// the population forms of the two one-wavefront integrators above (float32 fixed step,
+// adaptive RK23): grid (groups, replicas), mfma_population.hip, one unit per equation
+template <int kEq>
+void integrate_population_spec(const DevParams& p, const IntegrateArgs& a,
+                               const PopulationStrides& s, int groups, int replicas,
+                               hipStream_t stream);
+template <int kEq>
+void adaptive_population_spec(const DevParams& p, const AdaptiveArgs& a,
+                              const PopulationStrides& s, int groups, int replicas,
+                              hipStream_t stream);
+
 #define DDD_DECLARE_SPEC(EQ)                                                               \
   template <> void integrate_spec<EQ>(int, bool, bool, const DevParams&, const IntegrateArgs&, \
                                       int, hipStream_t);                                       \
@@ -80,7 +93,11 @@ void adaptive_spec(int rows, const DevParams& p, const AdaptiveArgs& a, int bloc
   template <> void step_half_spec<EQ>(const DevParams&, const StepArgs&, int, int, hipStream_t); \
   template <> void integrate_split_spec<EQ>(const DevParams&, const IntegrateArgs&, int, hipStream_t); \
   template <> void integrate_quad_spec<EQ>(const DevParams&, const IntegrateArgs&, int, hipStream_t); \
-  template <> void adaptive_quad_spec<EQ>(const DevParams&, const AdaptiveArgs&, int, hipStream_t);
+  template <> void adaptive_quad_spec<EQ>(const DevParams&, const AdaptiveArgs&, int, hipStream_t); \
+  template <> void integrate_population_spec<EQ>(const DevParams&, const IntegrateArgs&,       \
+                                                 const PopulationStrides&, int, int, hipStream_t); \
+  template <> void adaptive_population_spec<EQ>(const DevParams&, const AdaptiveArgs&,         \
+                                                const PopulationStrides&, int, int, hipStream_t);
 DDD_DECLARE_SPEC(0) DDD_DECLARE_SPEC(1) DDD_DECLARE_SPEC(2)
 DDD_DECLARE_SPEC(3) DDD_DECLARE_SPEC(4) DDD_DECLARE_SPEC(5)
 #undef DDD_DECLARE_SPEC

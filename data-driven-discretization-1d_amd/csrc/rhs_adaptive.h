@@ -131,14 +131,22 @@ struct AdaptiveShared {
 // workgroups 1600 next to Shared<256>)
 static_assert(sizeof(Shared<64>) + sizeof(AdaptiveShared<64>) <= 20 * 1024, "8 groups per CU");
 
-template <int kRows, int kWR, bool kHoist, int kEq, bool kWide = false, class TW = DefaultTower>
+// Pop: empty in every solo kernel.  The population form (mfma_population.hip: replicas on
+// grid.y) is this kernel with one more argument, Pop = PopulationStrides: workgroup
+// (g, r) then runs group g with replica r's weights into replica r's part of the outputs
+// (enter_replica, rhs_mfma.h) -- scalar arithmetic ahead of the set-up, nothing of it inside
+// the time loop.
+template <int kRows, int kWR, bool kHoist, int kEq, bool kWide = false, class TW = DefaultTower,
+          class... Pop>
 __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW, true>())) void adaptive_kernel(
-    DevParams p, AdaptiveArgs a) {
+    DevParams p, AdaptiveArgs a, Pop... pop) {
   __shared__ Shared<kRows, kWR, kWide, TW> sm;
   __shared__ AdaptiveShared<kRows> as;
   static_assert(kRows == kWR || kWide || !TW::kDefault ||
                     sizeof(Shared<kRows, kWR, kWide>) + sizeof(AdaptiveShared<kRows>) <= 80 * 1024,
                 "two 256-row workgroups per CU");
+  WeightShift ws;
+  if constexpr (sizeof...(Pop) != 0) ws = enter_replica(a, pop...);
   // reduction scratch of sample_sum: one-wave groups shuffle; four-wave groups use
   // Shared::un + Shared::flux (2 x kRows floats = kRows doubles), free between evaluations
   double* red = kRows == kWR ? nullptr : reinterpret_cast<double*>(sm.un);
@@ -147,7 +155,7 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW, true>(
   Resident res;
   // (no resident tower weights here: the controller state needs the registers -- with them
   // the streamed-tower adaptive kernels spill 3-16 VGPRs)
-  const bool fast_frc = launch_setup<kRows, kWR, kHoist, false>(p, sm, ln, a.batch, res);
+  const bool fast_frc = launch_setup<kRows, kWR, kHoist, false>(p, sm, ln, a.batch, res, ws);
   // sample whose (sample, mode) pair this lane evaluates in forcing phase 1
   const int frc_sl = (fast_frc && tid < (kRows / p.N) * p.P)
                          ? row_sample(tid, p.inv_P) : 0;

@@ -440,8 +440,8 @@ __device__ __forceinline__ void load_rows4(const float* __restrict__ base, int l
 }
 
 __device__ __forceinline__ void load_hidden(const DevParams& p, int hidden_index,
-                                            int lane, float (&w)[kHidSteps]) {
-  load_rows4<kHidSteps>(p.w_hidden + (size_t)hidden_index * padded_rows4(kHidSteps) * 64, lane, w);
+                                            int lane, float (&w)[kHidSteps], long long shift = 0) {
+  load_rows4<kHidSteps>(p.w_hidden + shift + (size_t)hidden_index * padded_rows4(kHidSteps) * 64, lane, w);
 }
 
 #define DDD_MFMA32(A, B, C) __builtin_amdgcn_mfma_f32_32x32x2f32((A), (B), (C), 0, 0, 0)
@@ -1427,6 +1427,38 @@ struct Resident {
 #endif
 };
 
+// Where the weights of a launch lie, in floats past DevParams::w_input / w_hidden / w_final4.
+// Zero in every kernel but the population forms of the per-equation one-wavefront
+// integrators (mfma_population.hip: replica r's panel), which load all their weights in
+// setup_weights: the kernel-argument block itself is never written, so its projection
+// tables stay scalar operands.
+struct WeightShift {
+  long long w_input = 0, w_hidden = 0, w_final4 = 0;
+};
+
+// Workgroup (g, r) of a population launch, r = blockIdx.y (wave-uniform): replica r's part of
+// the call's outputs, and where its weights lie.  y0, the output times and the forcing
+// tables are the replicas' common ones.
+__device__ __forceinline__ WeightShift replica_weights(const PopulationStrides& s, long long r) {
+  WeightShift ws;
+  ws.w_input = r * s.w_input;
+  ws.w_hidden = r * s.w_hidden;
+  ws.w_final4 = r * s.w_final4;
+  return ws;
+}
+__device__ __forceinline__ WeightShift enter_replica(AdaptiveArgs& a, const PopulationStrides& s) {
+  const long long r = (long long)blockIdx.y;
+  a.y_out += r * s.y_out;
+  a.nfev += r * s.samples;
+  a.status += r * s.samples;
+  return replica_weights(s, r);
+}
+__device__ __forceinline__ WeightShift enter_replica(IntegrateArgs& a, const PopulationStrides& s) {
+  const long long r = (long long)blockIdx.y;
+  a.y_out = static_cast<float*>(a.y_out) + r * s.y_out;   // (float32 state: the only population form)
+  return replica_weights(s, r);
+}
+
 // Forcing, phases 1 + 2, for time t:
 //   sum_j a_j sin(omega_j t + theta_j(x) + phi_j)
 //     = sum_j [a_j sin(psi_j)] cos(theta_j(x)) + [a_j cos(psi_j)] sin(theta_j(x)),
@@ -2280,7 +2312,8 @@ __device__ __forceinline__ void lane_offsets(const DevParams& p, const Lane& ln,
 // Per-launch setup, part 1: resident registers and the tables in LDS.
 template <int kRows, int kWR, bool kHoist, bool kKeepTower = true, bool kWide, class TW>
 __device__ __forceinline__ bool setup_weights(const DevParams& p, Shared<kRows, kWR, kWide, TW>& sm,
-                                              const Lane& ln, Resident& res) {
+                                              const Lane& ln, Resident& res,
+                                              const WeightShift& ws = WeightShift{}) {
   constexpr int kThreads = kRows / kWR * 64;
   const int tid = group_tid<kRows, kWR>();
   constexpr int kGW = flavour_stencil(kWide);
@@ -2341,13 +2374,13 @@ __device__ __forceinline__ bool setup_weights(const DevParams& p, Shared<kRows, 
     load_rows4<fin4_regs(4)>(p.w_final4, ln.lane, res.w_fin4);
   } else
   if (!p.fixed && !p.linear_taps && TW::kDefault) {   // (other towers stream every layer's weights)
-    load_rows4<kInSteps>(p.w_input, ln.lane, res.w_in);
-    if (kHoist) load_hidden(p, 0, ln.lane, res.hid);
+    load_rows4<kInSteps>(p.w_input + ws.w_input, ln.lane, res.w_in);
+    if (kHoist) load_hidden(p, 0, ln.lane, res.hid, ws.w_hidden);
     // loop invariants the specialised one-wave integrators keep resident
     // (kHoist: the persistent kernels; a single fused substep has no loop)
     if (kHoist && kWR == 64) {
       if (p.w_final4 != nullptr)   // (dead in the run-time kernels, null for wide models)
-        load_rows4<fin4_regs(4)>(p.w_final4, ln.lane, res.w_fin4);   // (zero padded to 4 groups)
+        load_rows4<fin4_regs(4)>(p.w_final4 + ws.w_final4, ln.lane, res.w_fin4);   // (zero padded to 4 groups)
     }
     if (kHoist && kWR == 32 && p.w_final4_split != nullptr) {
       // split integrators: this wavefront's chunk of channel groups (two chunks of
@@ -2415,8 +2448,9 @@ __device__ __forceinline__ bool setup_weights(const DevParams& p, Shared<kRows, 
 // Per-launch setup of the persistent integrators and the one-group substep kernel.
 template <int kRows, int kWR, bool kHoist, bool kKeepTower = true, bool kWide, class TW>
 __device__ __forceinline__ bool launch_setup(const DevParams& p, Shared<kRows, kWR, kWide, TW>& sm,
-                                             const Lane& ln, int batch, Resident& res) {
-  const bool fast = setup_weights<kRows, kWR, kHoist, kKeepTower>(p, sm, ln, res);
+                                             const Lane& ln, int batch, Resident& res,
+                                             const WeightShift& ws = WeightShift{}) {
+  const bool fast = setup_weights<kRows, kWR, kHoist, kKeepTower>(p, sm, ln, res, ws);
   setup_samples<kRows, kWR>(p, sm, (int)blockIdx.x, batch, res, fast);
   return fast;
 }
@@ -2703,14 +2737,19 @@ constexpr bool kTraceByDefault = true;
 #else
 constexpr bool kTraceByDefault = false;
 #endif
+// Pop: empty in every solo kernel; PopulationStrides in the population form
+// (mfma_population.hip: replicas on grid.y, enter_replica above).
 template <int kRows, int kWR, typename ST, bool kHoist, int kEq = -1,
-          bool kTrace = (kEq < 0) && kTraceByDefault, bool kWide = false, class TW = DefaultTower>
+          bool kTrace = (kEq < 0) && kTraceByDefault, bool kWide = false, class TW = DefaultTower,
+          class... Pop>
 __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW>())) void integrate_kernel(
-    DevParams p, IntegrateArgs a) {
+    DevParams p, IntegrateArgs a, Pop... pop) {
   __shared__ Shared<kRows, kWR, kWide, TW> sm;
+  WeightShift ws;
+  if constexpr (sizeof...(Pop) != 0) ws = enter_replica(a, pop...);
   const Lane ln = make_lane<kRows, kWR>(p, a.batch, (int)threadIdx.x, (int)blockIdx.x);
   Resident res;
-  const bool fast_frc = launch_setup<kRows, kWR, kHoist>(p, sm, ln, a.batch, res);
+  const bool fast_frc = launch_setup<kRows, kWR, kHoist>(p, sm, ln, a.batch, res, ws);
   // (Two wavefronts share each SIMD and run the same phases.  Static priorities
   // by hardware wave slot and start staggering were measured and change nothing
   // (profiles/r2_ablation.txt); the switches survive in the probe build only.)

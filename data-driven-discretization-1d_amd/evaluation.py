@@ -26,10 +26,14 @@ Arrays are plain NumPy: ``y_model`` [sample, time, x_low], ``y_exact``
 the device: a ``RolloutReference`` prepares what does not depend on the model
 once (the block-averaged exact solution, the error thresholds, the initial
 conditions), ``run_integrate_population`` enqueues the R rollouts side by side
-into one slab and ``ddd_rollout_scores`` scores them in two launches; one small
-host read returns ``mae`` [replica, time_max, sample] and ``survival`` [replica,
+into one slab -- or, with ``launch='population'``, rolls all of them out in ONE launch
+whose grid carries the replicas (``ddd_population_integrate_*``) -- and
+``ddd_rollout_scores`` scores them in two launches; one small host read returns
+``mae`` [replica, time_max, sample] and ``survival`` [replica,
 quantile, sample].
 """
+import atexit
+import ctypes
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -292,7 +296,8 @@ class RolloutReference(object):
 def run_integrate_population(models: Sequence[model_lib.LearnedStencilModel], hparams, y0,
                              times: np.ndarray, warmup: float = 0, max_step: float = 0.01,
                              scheme: str = 'bs3', adaptive: Optional[bool] = None,
-                             first_seed: int = 0, streams: int = 4):
+                             first_seed: int = 0, streams: int = 4,
+                             launch: str = 'streams'):
   """run_integrate_batch for R models of one equation at once, everything staying on the
   device: returns ``(y [replica, time, sample, x], nfev [replica, sample], status
   [replica, sample])`` as device tensors, replica r's part being what ``models[r]``
@@ -302,7 +307,23 @@ def run_integrate_population(models: Sequence[model_lib.LearnedStencilModel], hp
   The replicas are enqueued round-robin on ``min(R, streams)`` side streams that start
   behind the current stream and that the current stream then waits for; nothing waits on
   the host.  Single rank only: sharding stays with ``evaluate``.
+
+  ``launch``: 'streams' is the above.  'population' rolls all replicas out in one launch
+  on the current stream (``ddd_population_integrate_adaptive_f64`` /
+  ``ddd_population_integrate_fixed``: replicas on the grid's second dimension, the
+  forcing of every replica being ``models[0]``'s); configurations the library has no
+  population kernel for raise NotImplementedError with its reason.  'auto' takes that
+  route where it exists and the streams otherwise.  The tensors returned are the same
+  either way, bit for bit.  Unlike the streams route the population route waits on the
+  host once per call: building the per-call handle copies the replicas' packed weights
+  device to device and synchronises the device (``ddd_population_create``).  With the
+  fixed step it also takes a second ``[replica, time - 1, sample, x]`` buffer and one copy
+  of it, because the library's rows are replica-major without row 0.  The handle and the
+  models it references are released by the next population call whose launch has finished,
+  by ``release_populations()``, or at interpreter exit.
   """
+  if launch not in LAUNCHES:
+    raise ValueError('launch must be one of {}, got {!r}'.format(LAUNCHES, launch))
   torch = _lib.require_gpu()
   lib = _lib.load_library()
   if distributed.world_info()[2] > 1:
@@ -346,6 +367,15 @@ def run_integrate_population(models: Sequence[model_lib.LearnedStencilModel], hp
   if not adaptive:
     y[:, 0] = y0
     nfev.fill_(lib.ddd_scheme_stages(_lib.SCHEMES[scheme]) * num_steps)
+  if launch != 'streams':
+    try:
+      _population_rollout(lib, torch, models, adaptive, y0, warmup + times, max_step, scheme,
+                          num_steps if not adaptive else 0, save_every if not adaptive else 1,
+                          y, nfev, status)
+      return y, nfev, status
+    except NotImplementedError:
+      if launch == 'population':
+        raise
   current = torch.cuda.current_stream()
   side = [torch.cuda.Stream() for _ in range(min(len(models), int(streams)))]
   for stream in side:
@@ -361,6 +391,75 @@ def run_integrate_population(models: Sequence[model_lib.LearnedStencilModel], hp
   for stream in side:
     current.wait_stream(stream)
   return y, nfev, status
+
+
+LAUNCHES = ('streams', 'population', 'auto')
+
+# population handles whose launch may still be running: (event recorded behind the launch,
+# handle, the models -- models[0] is read by the launch, the others only kept alive)
+_PENDING = []
+
+
+def _reap_populations(lib, wait: bool = False):
+  """Destroy the population handles whose launches have finished (``wait``: all of them,
+  after waiting for their launches)."""
+  for entry in list(_PENDING):
+    event, handle, _ = entry
+    if wait:
+      event.synchronize()
+    if event.query():
+      lib.ddd_population_destroy(handle)
+      _PENDING.remove(entry)
+
+
+def release_populations():
+  """Wait for the population launches still in flight and free their handles (the weight
+  copies on the device) and the references to their models.  Also runs at interpreter
+  exit; call it to give the memory back earlier."""
+  if _PENDING and _lib._lib is not None:   # pylint: disable=protected-access
+    try:
+      _reap_populations(_lib._lib, wait=True)   # pylint: disable=protected-access
+    except RuntimeError:   # (at exit: the device runtime may be gone before this runs)
+      del _PENDING[:]
+
+
+atexit.register(release_populations)
+
+
+def _population_rollout(lib, torch, models, adaptive, y0, times, max_step, scheme, num_steps,
+                        save_every, y, nfev, status):
+  """One ddd_population_integrate_* call on the current stream into ``y`` / ``nfev`` /
+  ``status`` (run_integrate_population's buffers).  The handle is built from the models'
+  handles for this call and destroyed once its launch has run (_reap_populations, at the
+  next call); NotImplementedError where the library has no population kernel."""
+  _reap_populations(lib)
+  handles = (ctypes.c_void_p * len(models))(
+      *[m._handle.value for m in models])   # pylint: disable=protected-access
+  handle = ctypes.c_void_p()
+  _lib.check_supported(lib.ddd_population_create(handles, len(models), ctypes.byref(handle)))
+  try:
+    samples = int(y0.shape[0])
+    stream = _lib.current_stream()
+    if adaptive:
+      times = np.ascontiguousarray(times, dtype=np.float64)
+      _lib.check_supported(lib.ddd_population_integrate_adaptive_f64(
+          handle, times.ctypes.data_as(_lib._D), int(times.size), 1e-3, 1e-6, float(max_step),
+          0, y0.data_ptr(), y.data_ptr(), nfev.data_ptr(), status.data_ptr(), samples, stream))
+    else:
+      # (the library's rows are the saved states [replica, save, sample, x]; row 0 of y is y0)
+      saved = torch.empty((len(models), int(y.shape[1]) - 1) + tuple(y0.shape), dtype=y.dtype,
+                          device=y.device)
+      _lib.check_supported(lib.ddd_population_integrate_fixed(
+          handle, _lib.SCHEMES[scheme], float(times[0]), float(max_step), int(num_steps),
+          int(save_every), y0.data_ptr(), saved.data_ptr(), samples, stream))
+      y[:, 1:] = saved
+  except Exception:
+    torch.cuda.current_stream().synchronize()
+    lib.ddd_population_destroy(handle)
+    raise
+  event = torch.cuda.Event()
+  event.record()
+  _PENDING.append((event, handle, list(models)))
 
 
 def evaluate_population(models: Sequence[model_lib.LearnedStencilModel], hparams,

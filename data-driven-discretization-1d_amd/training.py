@@ -581,7 +581,7 @@ def rollout_metrics(result) -> List[Dict[str, float]]:
 def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], hparams,
                         init_seeds: Sequence[int], learning_rates=None, seed: int = 0,
                         num_steps: int = None, metrics: bool = False, select: str = None,
-                        rollout=None):
+                        rollout=None, rollout_launch: str = 'streams'):
   """training_loop(..., seed=seed, fused=True) for R replicas at once: the same dataset,
   train / validation split and minibatch order; replica r starts from
   LearnedStencilModel(coarse, hparams, init_seed=init_seeds[r]) and follows
@@ -599,7 +599,8 @@ def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], h
 
   rollout: an evaluation.RolloutReference; the exported models are then rolled out once
   after the last stretch (evaluation.evaluate_population) and the keys of rollout_metrics
-  are added to every replica's last row, where select can name them."""
+  are added to every replica's last row, where select can name them.  rollout_launch is
+  evaluate_population's ``launch`` ('streams', 'population' or 'auto')."""
   if len(checkpoint_dirs) != len(init_seeds):
     raise ValueError('one checkpoint directory per init seed')
   hparams = copy.deepcopy(hparams)
@@ -657,7 +658,8 @@ def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], h
     model.save(checkpoint_dir)
   if rollout is not None:
     from . import evaluation   # (evaluation does not import training)
-    scores = rollout_metrics(evaluation.evaluate_population(exported, hparams, rollout))
+    scores = rollout_metrics(evaluation.evaluate_population(exported, hparams, rollout,
+                                                            launch=rollout_launch))
     for replica_rows, row in zip(rows, scores):
       replica_rows[-1].update(row)
   if select is None:

@@ -820,6 +820,51 @@ DDD_API size_t ddd_rollout_scores_workspace_bytes(int replicas, int num_times, i
  * work. */
 DDD_API int ddd_rollout_scores(const ddd_rollout_scores_args* args, void* stream);
 
+/* ---- rollouts of a replica population in one launch ------------------------
+ * R models of ONE architecture that differ only in their weights, integrated by one
+ * launch whose grid is (groups, R): workgroup (g, r) is group g of a solo launch on
+ * `batch` samples, run with replica r's weights.  Replica r's part of every output is
+ * bit for bit what ddd_integrate_adaptive_f64 / ddd_integrate_fixed (persistent launch
+ * mode) writes for models[r] alone from the same y0, NaN rows included.
+ *
+ * ddd_population_create takes 1 <= replicas <= DDD_MAX_REPLICAS distinct model handles
+ * with identical ddd_config (equation, grid, tower, head, standard deviation; of
+ * derivative_orders[] and input_sizes[] the num_derivatives entries in use, reserved[] not
+ * at all) and equal projection tables, and copies each model's packed weights device to device: a later
+ * change to a model does not reach the population.  Carried: models on the MFMA route
+ * with the per-equation specialisation of the one-wavefront kernels, num_points dividing
+ * 64, no explicit ddd_set_kernel choice.  Everything else (num_points not dividing 64 --
+ * the 256-row geometry --, the run-time-parameterised, wide, other-tower and 16-channel-
+ * tile kernels, fixed stencils, WENO, spectral and generic models) returns
+ * DDD_ERR_UNSUPPORTED with the reason in ddd_last_error(): there is no fallback here,
+ * integrate such models one by one.
+ *
+ * Forcing: everything that is not a weight -- the forcing tables included -- is taken
+ * from models[0] AT CALL TIME.  models[0] must therefore outlive the population, and its
+ * forcing (ddd_set_forcing with >= batch rows) is the forcing of EVERY replica; the other
+ * models' forcing is not looked at.  ddd_population_create synchronises the device (the
+ * copies), so a caller that builds a population per call waits on the host once per call.
+ *
+ * The integrate entry points take the arguments of their solo twins (same checks, same
+ * max_attempts default) with replica-major outputs:
+ *   adaptive: y_out [R][n_times][batch][N] float64, nfev and status [R][batch]
+ *   fixed:    y_out [R][n_steps / save_every][batch][N] float32
+ * y0 [batch][N] and `times` are shared by the replicas.  Both end a chained region of
+ * models[0] (ddd_stream_fork) and only enqueue on `stream`; `times` travels through
+ * models[0]'s page-locked ring as in ddd_integrate_adaptive_f64.  ddd_population_destroy
+ * frees the weight copies at once: synchronise `stream` (or order the call behind its
+ * work) first. */
+typedef struct ddd_population ddd_population;
+DDD_API int ddd_population_create(ddd_model* const* models, int replicas, ddd_population** out);
+DDD_API int ddd_population_destroy(ddd_population* population);
+DDD_API int ddd_population_integrate_adaptive_f64(ddd_population* population,
+    const double* times, int n_times, double rtol, double atol, double max_step,
+    long long max_attempts, const double* y0, double* y_out, int32_t* nfev, int32_t* status,
+    int batch, void* stream);
+DDD_API int ddd_population_integrate_fixed(ddd_population* population, int scheme, double t0,
+    double dt, int n_steps, int save_every, const float* y0, float* y_out, int batch,
+    void* stream);
+
 /* ---- differentiable evaluation --------------------------------------------
  * Replaces: tf.gradients through model.predict_result (model.py:664-697), the
  * building block of the reference's differentiable time integration

@@ -12,13 +12,19 @@ versions alternated over `rounds` (at least 3) rounds:
   a  R x evaluation.evaluate
   b  evaluate_population(streams=1)
   c  evaluate_population(streams=4)
+  d  evaluate_population(launch='population'): all R rollouts in ONE launch, replicas on
+     the grid's second dimension (ddd_population_integrate_adaptive_f64)
   s  scoring alone, on trajectories resident on the device: NumPy after a host copy
      against the two launches and their host read
 Every timing starts behind a device synchronise and ends behind one, by wall clock; the
 RolloutReference is built before the clock starts (it does not depend on the models).
 Medians and the spread (max - min) / median over the rounds are reported.
 
-  python profiles/tools/rollout_population_throughput.py [--rounds 3]
+  python profiles/tools/rollout_population_throughput.py [--rounds 3] [--versions abcsd]
+
+--versions picks the versions that are alternated (a checkout from before version d
+existed is measured with its own copy of this tool: versions b and c there are the
+baseline of d here, profiles/rollout_population_one_launch.json).
 """
 import argparse
 import json
@@ -73,6 +79,8 @@ def measure(version, replicas, repeats):
   elif version in ('b', 'c'):
     streams = 1 if version == 'b' else 4
     call = lambda: evaluation.evaluate_population(models, hp, reference, streams=streams)
+  elif version == 'd':
+    call = lambda: evaluation.evaluate_population(models, hp, reference, launch='population')
   else:   # scoring alone: trajectories resident, (NumPy after a copy, the two launches)
     y, _, _ = evaluation.run_integrate_population(models, hp, reference.y0, TIMES)
     torch.cuda.synchronize()
@@ -113,6 +121,7 @@ def main():
   parser.add_argument('--rounds', type=int, default=3)
   parser.add_argument('--repeats', type=int, default=3, help='timed calls per child process')
   parser.add_argument('--replicas', type=int, nargs='*', default=REPLICAS)
+  parser.add_argument('--versions', default='abcsd', help='the versions alternated, of a b c s d')
   parser.add_argument('--version', default=None, help='one version in this process (the children)')
   args = parser.parse_args()
   if args.version is not None:
@@ -127,7 +136,7 @@ def main():
   for replicas in args.replicas:
     seconds = {}
     for _ in range(max(args.rounds, 3)):
-      for version in ('a', 'b', 'c', 's'):
+      for version in args.versions:
         done = subprocess.run(
             [sys.executable, os.path.abspath(__file__), '--version', version, '--replicas',
              str(replicas), '--repeats', str(args.repeats)],
