@@ -707,27 +707,10 @@ def train_unrolled_loss_grad(cfg, weights, y, labels, baseline, error_floor, coe
       nullspace, bias, sample_index, batch, want_grad, want_predictions, workspace)
 
 
-def train_run(cfg, weights, adam_m, adam_v, y, labels, baseline, sample_index,
-              learning_rates, error_floor, coef_abs, coef_rel, first_step=0,
-              betas=(0.9, 0.999), epsilon=1e-8, num_time_steps=0, time_step=0.0,
-              error_max=0.0, error_scale=None, nullspace=None, bias=None,
-              want_last_grad=False, workspace=None):
-  """ddd_train_run: len(learning_rates) optimiser steps enqueued on the current stream;
-  returns (head_means_log [num_steps, 2, H'] device tensor, last_grad or None) without
-  waiting for the device.
-
-  weights / adam_m / adam_v (flat, ddd_model_create layout) are updated in place;
-  sample_index is an int32 device tensor [num_steps, batch]; learning_rates host floats,
-  one per step (step k is optimiser step first_step + k + 1); error_floor / coef_abs /
-  coef_rel H' host floats; error_scale [2, H'] host floats (needed with error_max > 0).
-  The other arguments as train_loss_grad / train_unrolled_loss_grad."""
-  lib = load_library()
-  torch = require_gpu()
-  steps = int(num_time_steps)
-  if float(error_max or 0.0) > 0 and error_scale is None:
-    raise ValueError("error_max > 0 needs error_scale [2, H']")
-  rates = [float(rate) for rate in learning_rates]
-  num_steps = len(rates)
+def _check_training_data(cfg, steps, y, labels, baseline, nullspace, bias):
+  """What train_run, train_population_run and eval_metrics check of their dataset alike:
+  labels / baseline [S, N, H'] against cfg, y [S, N] and `steps` time steps, and every
+  tensor contiguous float32 on the device.  Returns H'."""
   heads = int(labels.shape[-1])
   if heads != cfg.num_derivatives + 1 + steps:
     raise ValueError('labels must have num_derivatives + 1 + num_time_steps = {} channels, '
@@ -735,124 +718,62 @@ def train_run(cfg, weights, adam_m, adam_v, y, labels, baseline, sample_index,
   if (y.dim() != 2 or tuple(labels.shape) != tuple(y.shape) + (heads,) or
       tuple(baseline.shape) != tuple(labels.shape) or y.shape[1] != cfg.num_points):
     raise ValueError("expected y [S, N], labels / baseline [S, N, H']")
-  if (not isinstance(sample_index, torch.Tensor) or sample_index.dtype != torch.int32 or
-      not sample_index.is_cuda or not sample_index.is_contiguous() or
-      sample_index.dim() != 2 or int(sample_index.shape[0]) != num_steps):
-    raise ValueError('sample_index must be a contiguous int32 device tensor '
-                     '[num_steps, batch]')
-  batch = int(sample_index.shape[1])
-  ws_bytes = lib.ddd_train_run_workspace_bytes(ctypes.byref(cfg), batch, steps)
-  if ws_bytes == 0:
-    check(-1)
-  _check_f32_device('weights', weights, (vjp_num_weights(cfg),))
-  _check_f32_device('adam_m', adam_m, tuple(weights.shape))
-  _check_f32_device('adam_v', adam_v, tuple(weights.shape))
   for name, tensor in (('y', y), ('labels', labels), ('baseline', baseline),
                        ('nullspace', nullspace), ('bias', bias)):
     if tensor is not None:
       _check_f32_device(name, tensor, tuple(tensor.shape))
-  if workspace is None or workspace.numel() < ws_bytes:
-    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
-  log = torch.empty((num_steps, 2, heads), dtype=torch.float32, device=y.device)
-  last_grad = torch.empty_like(weights) if want_last_grad else None
-  args = DDDTrainRunArgs()
-  args.struct_size = ctypes.sizeof(DDDTrainRunArgs)
-  args.batch = batch
-  args.num_rows = int(y.shape[0])
-  args.num_time_steps = steps
-  args.first_step = int(first_step)
-  args.num_steps = num_steps
-  for name, tensor in (('weights', weights), ('adam_m', adam_m), ('adam_v', adam_v),
-                       ('y', y), ('labels', labels), ('baseline', baseline),
-                       ('sample_index', sample_index), ('head_means_log', log)):
-    setattr(args, name, tensor.data_ptr())
-  args.nullspace = None if nullspace is None else nullspace.data_ptr()
-  args.bias = None if bias is None else bias.data_ptr()
-  rate_array = (ctypes.c_double * max(num_steps, 1))(*rates)
-  args.learning_rate = ctypes.cast(rate_array, ctypes.POINTER(ctypes.c_double))
-  args.beta1, args.beta2 = float(betas[0]), float(betas[1])
-  args.epsilon = float(epsilon)
-  args.error_max = float(error_max or 0.0)
-  for h in range(heads):
-    args.error_floor[h] = float(error_floor[h])
-    args.coef_abs[h] = float(coef_abs[h])
-    args.coef_rel[h] = float(coef_rel[h])
-    if error_scale is not None:
-      args.error_scale_abs[h] = float(error_scale[0][h])
-      args.error_scale_rel[h] = float(error_scale[1][h])
-  args.time_step = float(time_step)
-  args.last_grad = None if last_grad is None else last_grad.data_ptr()
-  args.workspace = workspace.data_ptr()
-  args.workspace_bytes = workspace.numel()
-  check(lib.ddd_train_run(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
-  return log, last_grad
+  return heads
 
 
-def train_population_run(cfg, weights, adam_m, adam_v, y, labels, baseline, sample_index,
-                         learning_rates, error_floor, coef_abs, coef_rel, first_step=0,
-                         betas=(0.9, 0.999), epsilon=1e-8, num_time_steps=0, time_step=0.0,
-                         error_max=0.0, error_scale=None, nullspace=None, bias=None,
-                         want_last_grad=False, workspace=None):
-  """ddd_train_population_run: train_run on R replicas in one call; returns
-  (head_means_log [num_steps, R, 2, H'] device tensor, last_grad [R, n_weights] or None)
-  without waiting for the device.
-
-  weights / adam_m / adam_v are [R, n_weights] (rows in the ddd_model_create layout; a
-  tensor with more rows is taken as its first R), updated in place; learning_rates host
-  floats [R][num_steps]; sample_index an int32 device tensor [num_steps, batch] (one
-  minibatch order for all replicas) or [num_steps, R, batch].  The other arguments, shared
-  by the replicas, as train_run."""
-  lib = load_library()
+def _train_run_call(entry, args, workspace_bytes, replicas, rates, cfg, weights, adam_m, adam_v,
+                    y, labels, baseline, sample_index, error_floor, coef_abs, coef_rel,
+                    first_step, betas, epsilon, num_time_steps, time_step, error_max,
+                    error_scale, nullspace, bias, want_last_grad, workspace):
+  """The body of train_run (replicas None: flat weights / adam_m / adam_v, sample_index
+  [num_steps, batch]) / train_population_run (replicas R): shape checks, workspace,
+  outputs and `args` (a DDDTrainRunArgs, or a DDDTrainPopulationArgs with its own fields
+  already set) filled, then `entry`.  rates: R rows (one for train_run) of num_steps host
+  floats; workspace_bytes(batch) is the entry point's workspace size.  Returns
+  (head_means_log [num_steps, R, 2, H'], last_grad [R, n_weights] or None)."""
   torch = require_gpu()
+  solo = replicas is None
+  rows = 1 if solo else replicas
   steps = int(num_time_steps)
   if float(error_max or 0.0) > 0 and error_scale is None:
     raise ValueError("error_max > 0 needs error_scale [2, H']")
-  rates = [[float(rate) for rate in row] for row in learning_rates]
-  replicas = len(rates)
   num_steps = len(rates[0]) if rates else 0
-  if any(len(row) != num_steps for row in rates):
-    raise ValueError('learning_rates must be [R][num_steps]')
-  heads = int(labels.shape[-1])
-  if heads != cfg.num_derivatives + 1 + steps:
-    raise ValueError('labels must have num_derivatives + 1 + num_time_steps = {} channels, '
-                     'got {}'.format(cfg.num_derivatives + 1 + steps, heads))
-  if (y.dim() != 2 or tuple(labels.shape) != tuple(y.shape) + (heads,) or
-      tuple(baseline.shape) != tuple(labels.shape) or y.shape[1] != cfg.num_points):
-    raise ValueError("expected y [S, N], labels / baseline [S, N, H']")
+  heads = _check_training_data(cfg, steps, y, labels, baseline, nullspace, bias)
   if (not isinstance(sample_index, torch.Tensor) or sample_index.dtype != torch.int32 or
       not sample_index.is_cuda or not sample_index.is_contiguous() or
-      sample_index.dim() not in (2, 3) or int(sample_index.shape[0]) != num_steps or
-      (sample_index.dim() == 3 and int(sample_index.shape[1]) != replicas)):
+      sample_index.dim() not in ((2,) if solo else (2, 3)) or
+      int(sample_index.shape[0]) != num_steps or
+      (sample_index.dim() == 3 and int(sample_index.shape[1]) != rows)):
     raise ValueError('sample_index must be a contiguous int32 device tensor '
-                     '[num_steps, batch] or [num_steps, R, batch]')
+                     '[num_steps, batch]' + ('' if solo else ' or [num_steps, R, batch]'))
   batch = int(sample_index.shape[-1])
-  ws_bytes = lib.ddd_train_population_workspace_bytes(ctypes.byref(cfg), batch, steps, replicas)
+  ws_bytes = workspace_bytes(batch)
   if ws_bytes == 0:
     check(-1)
   n_weights = vjp_num_weights(cfg)
   for name, tensor in (('weights', weights), ('adam_m', adam_m), ('adam_v', adam_v)):
-    rows = int(tensor.shape[0]) if isinstance(tensor, torch.Tensor) and tensor.dim() == 2 else 0
-    if rows < replicas:
-      raise ValueError('{} must be [R, n_weights] with R = {} rows'.format(name, replicas))
-    _check_f32_device(name, tensor, (rows, n_weights))
-  for name, tensor in (('y', y), ('labels', labels), ('baseline', baseline),
-                       ('nullspace', nullspace), ('bias', bias)):
-    if tensor is not None:
-      _check_f32_device(name, tensor, tuple(tensor.shape))
+    if solo:
+      _check_f32_device(name, tensor, (n_weights,))
+      continue
+    given = int(tensor.shape[0]) if isinstance(tensor, torch.Tensor) and tensor.dim() == 2 else 0
+    if given < rows:
+      raise ValueError('{} must be [R, n_weights] with R = {} rows'.format(name, rows))
+    _check_f32_device(name, tensor, (given, n_weights))
   if workspace is None or workspace.numel() < ws_bytes:
     workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
-  log = torch.empty((num_steps, replicas, 2, heads), dtype=torch.float32, device=y.device)
-  last_grad = (torch.empty((replicas, n_weights), dtype=torch.float32, device=y.device)
+  log = torch.empty((num_steps, rows, 2, heads), dtype=torch.float32, device=y.device)
+  last_grad = (torch.empty((rows, n_weights), dtype=torch.float32, device=y.device)
                if want_last_grad else None)
-  args = DDDTrainPopulationArgs()
-  args.struct_size = ctypes.sizeof(DDDTrainPopulationArgs)
+  args.struct_size = ctypes.sizeof(args)
   args.batch = batch
   args.num_rows = int(y.shape[0])
   args.num_time_steps = steps
   args.first_step = int(first_step)
   args.num_steps = num_steps
-  args.replicas = replicas
-  args.index_per_replica = 1 if sample_index.dim() == 3 else 0
   for name, tensor in (('weights', weights), ('adam_m', adam_m), ('adam_v', adam_v),
                        ('y', y), ('labels', labels), ('baseline', baseline),
                        ('sample_index', sample_index), ('head_means_log', log)):
@@ -876,8 +797,66 @@ def train_population_run(cfg, weights, adam_m, adam_v, y, labels, baseline, samp
   args.last_grad = None if last_grad is None else last_grad.data_ptr()
   args.workspace = workspace.data_ptr()
   args.workspace_bytes = workspace.numel()
-  check(lib.ddd_train_population_run(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
+  check(entry(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
   return log, last_grad
+
+
+def train_run(cfg, weights, adam_m, adam_v, y, labels, baseline, sample_index,
+              learning_rates, error_floor, coef_abs, coef_rel, first_step=0,
+              betas=(0.9, 0.999), epsilon=1e-8, num_time_steps=0, time_step=0.0,
+              error_max=0.0, error_scale=None, nullspace=None, bias=None,
+              want_last_grad=False, workspace=None):
+  """ddd_train_run: len(learning_rates) optimiser steps enqueued on the current stream;
+  returns (head_means_log [num_steps, 2, H'] device tensor, last_grad or None) without
+  waiting for the device.
+
+  weights / adam_m / adam_v (flat, ddd_model_create layout) are updated in place;
+  sample_index is an int32 device tensor [num_steps, batch]; learning_rates host floats,
+  one per step (step k is optimiser step first_step + k + 1); error_floor / coef_abs /
+  coef_rel H' host floats; error_scale [2, H'] host floats (needed with error_max > 0).
+  The other arguments as train_loss_grad / train_unrolled_loss_grad."""
+  lib = load_library()
+  steps = int(num_time_steps)
+  rates = [[float(rate) for rate in learning_rates]]
+  log, last_grad = _train_run_call(
+      lib.ddd_train_run, DDDTrainRunArgs(),
+      lambda b: lib.ddd_train_run_workspace_bytes(ctypes.byref(cfg), b, steps), None, rates,
+      cfg, weights, adam_m, adam_v, y, labels, baseline, sample_index, error_floor, coef_abs,
+      coef_rel, first_step, betas, epsilon, steps, time_step, error_max, error_scale,
+      nullspace, bias, want_last_grad, workspace)
+  return log[:, 0], None if last_grad is None else last_grad[0]
+
+
+def train_population_run(cfg, weights, adam_m, adam_v, y, labels, baseline, sample_index,
+                         learning_rates, error_floor, coef_abs, coef_rel, first_step=0,
+                         betas=(0.9, 0.999), epsilon=1e-8, num_time_steps=0, time_step=0.0,
+                         error_max=0.0, error_scale=None, nullspace=None, bias=None,
+                         want_last_grad=False, workspace=None):
+  """ddd_train_population_run: train_run on R replicas in one call; returns
+  (head_means_log [num_steps, R, 2, H'] device tensor, last_grad [R, n_weights] or None)
+  without waiting for the device.
+
+  weights / adam_m / adam_v are [R, n_weights] (rows in the ddd_model_create layout; a
+  tensor with more rows is taken as its first R), updated in place; learning_rates host
+  floats [R][num_steps]; sample_index an int32 device tensor [num_steps, batch] (one
+  minibatch order for all replicas) or [num_steps, R, batch].  The other arguments, shared
+  by the replicas, as train_run."""
+  lib = load_library()
+  steps = int(num_time_steps)
+  rates = [[float(rate) for rate in row] for row in learning_rates]
+  replicas = len(rates)
+  if any(len(row) != len(rates[0]) for row in rates):
+    raise ValueError('learning_rates must be [R][num_steps]')
+  args = DDDTrainPopulationArgs()
+  args.replicas = replicas
+  args.index_per_replica = (
+      1 if isinstance(sample_index, _torch().Tensor) and sample_index.dim() == 3 else 0)
+  return _train_run_call(
+      lib.ddd_train_population_run, args,
+      lambda b: lib.ddd_train_population_workspace_bytes(ctypes.byref(cfg), b, steps, replicas),
+      replicas, rates, cfg, weights, adam_m, adam_v, y, labels, baseline, sample_index,
+      error_floor, coef_abs, coef_rel, first_step, betas, epsilon, steps, time_step, error_max,
+      error_scale, nullspace, bias, want_last_grad, workspace)
 
 
 def eval_metrics(cfg, weights, y, labels, baseline, error_floor, coef_abs, coef_rel,
@@ -896,22 +875,12 @@ def eval_metrics(cfg, weights, y, labels, baseline, error_floor, coef_abs, coef_
   lib = load_library()
   torch = require_gpu()
   steps = int(num_time_steps)
-  heads = int(labels.shape[-1])
-  if heads != cfg.num_derivatives + 1 + steps:
-    raise ValueError('labels must have num_derivatives + 1 + num_time_steps = {} channels, '
-                     'got {}'.format(cfg.num_derivatives + 1 + steps, heads))
-  if (y.dim() != 2 or tuple(labels.shape) != tuple(y.shape) + (heads,) or
-      tuple(baseline.shape) != tuple(labels.shape) or y.shape[1] != cfg.num_points):
-    raise ValueError("expected y [S, N], labels / baseline [S, N, H']")
+  heads = _check_training_data(cfg, steps, y, labels, baseline, nullspace, bias)
   n_weights = vjp_num_weights(cfg)
   if not isinstance(weights, torch.Tensor) or weights.dim() != 2:
     raise ValueError('weights must be [R, n_weights]')
   replicas = int(weights.shape[0])
   _check_f32_device('weights', weights, (replicas, n_weights))
-  for name, tensor in (('y', y), ('labels', labels), ('baseline', baseline),
-                       ('nullspace', nullspace), ('bias', bias)):
-    if tensor is not None:
-      _check_f32_device(name, tensor, tuple(tensor.shape))
   if sample_index is not None:
     if (not isinstance(sample_index, torch.Tensor) or sample_index.dtype != torch.int32 or
         not sample_index.is_cuda or not sample_index.is_contiguous() or

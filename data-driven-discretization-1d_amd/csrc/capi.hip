@@ -38,7 +38,6 @@
 #include "train.h"
 #include "train_metrics.h"
 #include "train_population.h"
-#include "train_run.h"
 #include "train_unrolled.h"
 #include "rhs_weno.h"   // (host side only: weno::supports; the kernels are weno_unit.hip)
 
@@ -1512,7 +1511,7 @@ int train_unrolled_params(const ddd_config* cfg, int batch, int num_time_steps,
   return DDD_OK;
 }
 
-// The configuration checks and kernel parameters of ddd_train_run (train_run.h):
+// The configuration checks and kernel parameters of ddd_train_run (train_population.h):
 // train_params into r->q.t for num_time_steps = 0 (r->q.T = 0), train_unrolled_params
 // otherwise, named "training run" (ddd_train_population_run: "training population"); the
 // workspace is theirs plus the coefficient table.
@@ -1588,6 +1587,54 @@ int eval_metrics_params(const ddd_config* cfg, int rows_evaluated, int num_time_
   return DDD_OK;
 }
 
+// What every entry point that runs the training kernels checks first of the dataset it is
+// given, for any of their argument structs (equally named fields): nullspace / bias where
+// the configuration of p projects, and num_rows.
+inline bool projects(const ddd::train::TrainParams& p) {
+  return p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
+}
+
+template <typename Args>
+int check_dataset_args(const Args* a, const ddd::train::TrainParams& p) {
+  if (projects(p) && (!a->nullspace || !a->bias))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "nullspace/bias required for model_target 'coefficients' with "
+                "polynomial_accuracy_order > 0");
+  if (a->num_rows < 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
+  return DDD_OK;
+}
+
+// ... and last, behind the checks of its own: the workspace of at least ws bytes
+// (ws_bytes_fn names the entry point's workspace function in the message), the `heads`
+// per-head loss constants, finite, into floor / coef_abs / coef_rel, and the dataset and
+// workspace pointers into p.
+template <typename Args>
+int take_dataset_args(const Args* a, ddd::train::TrainParams& p, size_t ws,
+                      const char* ws_bytes_fn, int heads, float* floor, float* coef_abs,
+                      float* coef_rel) {
+  if (a->workspace == nullptr || a->workspace_bytes < ws)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "workspace of %zu bytes given, %s = %zu",
+                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws_bytes_fn, ws);
+  for (int h = 0; h < heads; ++h) {
+    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
+        !std::isfinite(a->coef_rel[h]))
+      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
+    floor[h] = a->error_floor[h];
+    coef_abs[h] = a->coef_abs[h];
+    coef_rel[h] = a->coef_rel[h];
+  }
+  p.weights = a->weights;
+  p.nullspace = projects(p) ? a->nullspace : nullptr;
+  p.bias = projects(p) ? a->bias : nullptr;
+  p.y = a->y;
+  p.rows = a->num_rows;
+  p.labels = a->labels;
+  p.baseline = a->baseline;
+  p.ws = static_cast<float*>(a->workspace);
+  return DDD_OK;
+}
+
 // What ddd_train_run and ddd_train_population_run check and copy alike, for Args =
 // ddd_train_run_args / ddd_train_population_args (equally named fields): the arguments
 // into r, whose configuration train_run_params has filled.  ws: the bytes the workspace
@@ -1603,13 +1650,8 @@ int train_run_args(const Args* a, ddd::train::RunParams& r, size_t ws, size_t ta
     return fail(DDD_ERR_INVALID_ARGUMENT,
                 "weights, adam_m, adam_v, y, labels, baseline, sample_index, learning_rate "
                 "and head_means_log must not be NULL");
-  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
-  if (projected && (!a->nullspace || !a->bias))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "nullspace/bias required for model_target 'coefficients' with "
-                "polynomial_accuracy_order > 0");
-  if (a->num_rows < 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
+  int rc = check_dataset_args(a, p);
+  if (rc) return rc;
   if (a->num_steps < 1)
     return fail(DDD_ERR_INVALID_ARGUMENT, "num_steps = %d (>= 1)", a->num_steps);
   if (a->first_step < 0)
@@ -1633,36 +1675,24 @@ int train_run_args(const Args* a, ddd::train::RunParams& r, size_t ws, size_t ta
     return fail(DDD_ERR_INVALID_ARGUMENT, "error_max = %g (>= 0)", a->error_max);
   if (a->num_time_steps > 0 && !std::isfinite(a->time_step))
     return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
-  if (a->workspace == nullptr || a->workspace_bytes < ws)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "workspace of %zu bytes given, %s = %zu",
-                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws_bytes_fn, ws);
+  rc = take_dataset_args(a, p, ws, ws_bytes_fn, r.heads, r.floor, r.coef_abs, r.coef_rel);
+  if (rc) return rc;
   for (int h = 0; h < r.heads; ++h) {
-    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
-        !std::isfinite(a->coef_rel[h]))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
     if (a->error_max > 0.0 &&
         (!std::isfinite(a->error_scale_abs[h]) || !std::isfinite(a->error_scale_rel[h])))
       return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_scale of head %d", h);
-    r.floor[h] = r.q.floor[h] = a->error_floor[h];
-    r.coef_abs[h] = r.q.coef_abs[h] = a->coef_abs[h];
-    r.coef_rel[h] = r.q.coef_rel[h] = a->coef_rel[h];
+    r.q.floor[h] = r.floor[h];
+    r.q.coef_abs[h] = r.coef_abs[h];
+    r.q.coef_rel[h] = r.coef_rel[h];
     if (r.q.T == 0) {   // (heads = H <= kMaxHeads)
-      p.floor[h] = a->error_floor[h];
-      p.coef_abs[h] = a->coef_abs[h];
-      p.coef_rel[h] = a->coef_rel[h];
+      p.floor[h] = r.floor[h];
+      p.coef_abs[h] = r.coef_abs[h];
+      p.coef_rel[h] = r.coef_rel[h];
     }
     r.scale_abs[h] = a->error_scale_abs[h];
     r.scale_rel[h] = a->error_scale_rel[h];
   }
-  p.weights = a->weights;
-  p.nullspace = projected ? a->nullspace : nullptr;
-  p.bias = projected ? a->bias : nullptr;
-  p.y = a->y;
-  p.rows = a->num_rows;
-  p.labels = a->labels;
-  p.baseline = a->baseline;
   p.predictions = nullptr;
-  p.ws = static_cast<float*>(a->workspace);
   r.q.dt = a->time_step;
   r.first_step = a->first_step;
   r.num_steps = a->num_steps;
@@ -1691,40 +1721,18 @@ int train_args(const Args* a, ddd::train::TrainParams& p, size_t ws, const char*
   if (!a->weights || !a->y || !a->labels || !a->baseline || !a->head_means)
     return fail(DDD_ERR_INVALID_ARGUMENT,
                 "weights, y, labels, baseline and head_means must not be NULL");
-  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
-  if (projected && (!a->nullspace || !a->bias))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "nullspace/bias required for model_target 'coefficients' with "
-                "polynomial_accuracy_order > 0");
-  if (a->num_rows < 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
+  int rc = check_dataset_args(a, p);
+  if (rc) return rc;
   if (a->sample_index == nullptr && a->batch > a->num_rows)
     return fail(DDD_ERR_INVALID_ARGUMENT,
                 "batch = %d > num_rows = %d without a sample_index", a->batch, a->num_rows);
   if constexpr (std::is_same<Args, ddd_train_unrolled_args>::value)
     if (!std::isfinite(a->time_step))
       return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
-  if (a->workspace == nullptr || a->workspace_bytes < ws)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "workspace of %zu bytes given, %s = %zu",
-                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws_bytes_fn, ws);
-  for (int h = 0; h < heads; ++h) {
-    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
-        !std::isfinite(a->coef_rel[h]))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
-    floor[h] = a->error_floor[h];
-    coef_abs[h] = a->coef_abs[h];
-    coef_rel[h] = a->coef_rel[h];
-  }
-  p.weights = a->weights;
-  p.nullspace = projected ? a->nullspace : nullptr;
-  p.bias = projected ? a->bias : nullptr;
-  p.y = a->y;
+  rc = take_dataset_args(a, p, ws, ws_bytes_fn, heads, floor, coef_abs, coef_rel);
+  if (rc) return rc;
   p.sample_index = a->sample_index;
-  p.rows = a->num_rows;
-  p.labels = a->labels;
-  p.baseline = a->baseline;
   p.predictions = a->predictions;
-  p.ws = static_cast<float*>(a->workspace);
   p.want_grad = a->grad != nullptr ? 1 : 0;
   p.grad = a->grad;
   p.head_means = a->head_means;
@@ -3047,14 +3055,17 @@ int ddd_train_run(const ddd_config* cfg, const ddd_train_run_args* a, void* stre
     return fail(DDD_ERR_INVALID_ARGUMENT,
                 "ddd_train_run_args.struct_size = %d, library expects %d (ABI mismatch)",
                 a->struct_size, (int)sizeof(ddd_train_run_args));
-  ddd::train::RunParams r;
+  // the population of one: its slabs, then its coefficient table
+  ddd::train::PopulationParams pp;
   size_t ws = 0;
-  int rc = train_run_params(cfg, a->batch, a->num_time_steps, &r, &ws);
+  int rc = train_run_params(cfg, a->batch, a->num_time_steps, &pp.r, &ws);
   if (rc) return rc;
-  rc = train_run_args(a, r, ws, ws - ddd::train::kCoefTableBytes, 0,
+  rc = train_run_args(a, pp.r, ws, ws - ddd::train::kCoefTableBytes, 0,
                       "ddd_train_run_workspace_bytes");
   if (rc) return rc;
-  DDD_HIP(ddd::train::launch_train_run(r, static_cast<hipStream_t>(stream)));
+  pp.replicas = 1;
+  pp.index_per_replica = 0;
+  DDD_HIP(ddd::train::launch_train_population(pp, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }
 
@@ -3117,13 +3128,8 @@ int ddd_eval_metrics(const ddd_config* cfg, const ddd_eval_metrics_args* a, void
   if (!a->weights || !a->y || !a->labels || !a->baseline || !a->sums || !a->below)
     return fail(DDD_ERR_INVALID_ARGUMENT,
                 "weights, y, labels, baseline, sums and below must not be NULL");
-  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
-  if (projected && (!a->nullspace || !a->bias))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "nullspace/bias required for model_target 'coefficients' with "
-                "polynomial_accuracy_order > 0");
-  if (a->num_rows < 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
+  rc = check_dataset_args(a, p);
+  if (rc) return rc;
   if (a->sample_index == nullptr && a->rows_evaluated > a->num_rows)
     return fail(DDD_ERR_INVALID_ARGUMENT,
                 "rows_evaluated = %d > num_rows = %d without a sample_index",
@@ -3132,29 +3138,12 @@ int ddd_eval_metrics(const ddd_config* cfg, const ddd_eval_metrics_args* a, void
     return fail(DDD_ERR_INVALID_ARGUMENT, "index_per_replica = 1 without a sample_index");
   if (a->num_time_steps > 0 && !std::isfinite(a->time_step))
     return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
-  if (a->workspace == nullptr || a->workspace_bytes < ws)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "workspace of %zu bytes given, ddd_eval_metrics_workspace_bytes = %zu",
-                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws);
-  for (int h = 0; h < q.HT; ++h) {
-    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
-        !std::isfinite(a->coef_rel[h]))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
-    q.floor[h] = a->error_floor[h];
-    q.coef_abs[h] = a->coef_abs[h];
-    q.coef_rel[h] = a->coef_rel[h];
-  }
-  p.weights = a->weights;
-  p.nullspace = projected ? a->nullspace : nullptr;
-  p.bias = projected ? a->bias : nullptr;
-  p.y = a->y;
+  rc = take_dataset_args(a, p, ws, "ddd_eval_metrics_workspace_bytes", q.HT, q.floor, q.coef_abs,
+                         q.coef_rel);
+  if (rc) return rc;
   p.sample_index = a->sample_index;
   p.index_stride = a->index_per_replica ? p.batch : 0;
-  p.rows = a->num_rows;
-  p.labels = a->labels;
-  p.baseline = a->baseline;
   p.predictions = a->predictions;
-  p.ws = static_cast<float*>(a->workspace);
   q.dt = a->time_step;
   m.sums = a->sums;
   m.below = a->below;

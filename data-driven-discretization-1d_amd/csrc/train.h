@@ -64,7 +64,8 @@ struct TrainParams {
   float* grad;             // [n_weights] or null
   float* head_means;       // [2][H]
   const float* coef_table; // device [3][heads]: floor, coef_abs, coef_rel, read instead of the
-                           // host values by the kernels built for it (train_run.h), or null
+                           // host values by the kernels built for it (train_population.h),
+                           // or null
 };
 
 static_assert(offsetof(TrainParams, grad) == offsetof(TrainParams, index_stride) + 4 &&
@@ -92,19 +93,12 @@ hipError_t launch_then_sum(const void* kernel, const void* params, const TrainPa
                            int blocks, size_t lds_bytes, hipStream_t stream, int first,
                            int total);
 
-// launch_then_sum in its two halves, for a caller that launches the same kernel many times
-// (train_run.hip): the dynamic-LDS attribute of `kernel`, once, and the launches without it
+// The dynamic-LDS attribute of `kernel`, for a caller that sets it once and then launches
+// the kernel many times itself (train_population.hip, train_metrics.hip)
 hipError_t set_dynamic_lds(const void* kernel, size_t lds_bytes);
-hipError_t launch_prepared_then_sum(const void* kernel, const void* params, const TrainParams& p,
-                                    int blocks, size_t lds_bytes, hipStream_t stream, int first,
-                                    int total);
 
 // loss_grad_kernel on `blocks` workgroups, then the slab sum (train.hip)
 hipError_t launch_loss_grad(const TrainParams& p, int blocks, size_t lds_bytes, hipStream_t stream);
-
-// loss_grad_kernel, or its twin that reads the loss constants from p.coef_table, as
-// launch_then_sum's `kernel` (train_run.hip launches them with a sum of its own)
-const void* loss_grad_kernel_entry(bool coef_table);
 
 // The vector-Jacobian product of one model evaluation (ddd_result_vjp, vjp.hip): the
 // forward pass of training, then, with a cotangent, the same backward pass from that

@@ -14,10 +14,6 @@ __global__ __launch_bounds__(kThreads) void loss_grad_kernel(TrainParams p) {
   loss_grad_body<false>(p);
 }
 
-__global__ __launch_bounds__(kThreads) void loss_grad_table_kernel(TrainParams p) {
-  loss_grad_body<true>(p);
-}
-
 // out[i] = sum over workgroups b (in order) of ws[b stride + i] for first <= i < total:
 // grad below n_weights, behind it the head sums as means over `count` = batch N
 __global__ __launch_bounds__(kThreads) void slab_sum_kernel(const float* ws, size_t stride,
@@ -36,11 +32,13 @@ hipError_t set_dynamic_lds(const void* kernel, size_t lds_bytes) {
   return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
 }
 
-hipError_t launch_prepared_then_sum(const void* kernel, const void* params, const TrainParams& p,
-                                    int blocks, size_t lds_bytes, hipStream_t stream, int first,
-                                    int total) {
+hipError_t launch_then_sum(const void* kernel, const void* params, const TrainParams& p,
+                           int blocks, size_t lds_bytes, hipStream_t stream, int first,
+                           int total) {
+  hipError_t err = set_dynamic_lds(kernel, lds_bytes);
+  if (err != hipSuccess) return err;
   void* args[] = {const_cast<void*>(params)};
-  hipError_t err = hipLaunchKernel(kernel, dim3(blocks), dim3(kThreads), args, lds_bytes, stream);
+  err = hipLaunchKernel(kernel, dim3(blocks), dim3(kThreads), args, lds_bytes, stream);
   if (err != hipSuccess || first >= total) return err;
   const int grid = (total + kThreads - 1) / kThreads;
   hipLaunchKernelGGL(slab_sum_kernel, dim3(grid), dim3(kThreads), 0, stream, p.ws, p.slab_stride,
@@ -49,22 +47,9 @@ hipError_t launch_prepared_then_sum(const void* kernel, const void* params, cons
   return hipGetLastError();
 }
 
-hipError_t launch_then_sum(const void* kernel, const void* params, const TrainParams& p,
-                           int blocks, size_t lds_bytes, hipStream_t stream, int first,
-                           int total) {
-  hipError_t err = set_dynamic_lds(kernel, lds_bytes);
-  if (err != hipSuccess) return err;
-  return launch_prepared_then_sum(kernel, params, p, blocks, lds_bytes, stream, first, total);
-}
-
 hipError_t launch_loss_grad(const TrainParams& p, int blocks, size_t lds_bytes, hipStream_t stream) {
   return launch_then_sum(reinterpret_cast<const void*>(loss_grad_kernel), &p, p, blocks, lds_bytes,
                          stream, p.want_grad ? 0 : p.n_weights, p.n_weights + 2 * p.H);
-}
-
-const void* loss_grad_kernel_entry(bool coef_table) {
-  return coef_table ? reinterpret_cast<const void*>(loss_grad_table_kernel)
-                    : reinterpret_cast<const void*>(loss_grad_kernel);
 }
 
 }  // namespace train

@@ -1,5 +1,5 @@
-// The body of the fused loss-and-gradient kernel (train.h), shared by loss_grad_kernel /
-// loss_grad_table_kernel (train.hip) and their replica forms (train_population.hip).  A
+// The body of the fused loss-and-gradient kernel (train.h), shared by loss_grad_kernel
+// (train.hip) and the replica forms of the optimiser loop (train_population.hip).  A
 // workgroup is blockIdx.x of gridDim.x; whatever else a kernel's grid has is the caller's.
 #pragma once
 #include <hip/hip_runtime.h>

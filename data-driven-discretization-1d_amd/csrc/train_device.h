@@ -188,7 +188,8 @@ __device__ __forceinline__ HeadTerms head_terms(float pv, float lv, float bv, fl
 
 // head_terms of head h with the loss constants of the call: the host values the kernel
 // arguments carry (floor / coef_abs / coef_rel, TrainParams' or UnrolledParams'), or with
-// kCoefTable the device table p.coef_table [3][heads] that clip_kernel (train_run.hip) wrote.
+// kCoefTable the device table p.coef_table [3][heads] that clip_population_kernel
+// (train_population.hip) wrote.
 // A template flag, not a run-time null: the kernels of the host values compile as before.
 template <bool kCoefTable, bool kReplicas = false>
 __device__ __forceinline__ HeadTerms head_terms_of(const TrainParams& p, const float* floor,

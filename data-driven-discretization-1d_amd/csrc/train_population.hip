@@ -1,7 +1,8 @@
-// ddd_train_population_run's device code and launcher (train_population.h): the four
-// loss kernels with a replica dimension, slab_adam_population_kernel,
-// slab_heads_population_kernel, clip_population_kernel and the host loop that enqueues
-// the steps.
+// The device code and launcher of ddd_train_run and ddd_train_population_run
+// (train_population.h): the four loss kernels with a replica dimension,
+// slab_adam_population_kernel (the slab sum with the optimiser folded in),
+// slab_heads_population_kernel, clip_population_kernel (error_max decided on the device)
+// and the host loop that enqueues the steps.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -13,9 +14,11 @@
 namespace ddd {
 namespace train {
 
-// The bodies of the solo kernels with kReplicas (train_device.h: weights_of): workgroup
-// (b, r) is workgroup b of gridDim.x on replica r's weights, slabs, index and table.  The
-// parameter struct is replica 0's and is read from the kernel arguments as it is.
+// The bodies of loss_grad_kernel / unrolled_loss_grad_kernel with kReplicas
+// (train_device.h: weights_of): workgroup (b, r) is workgroup b of gridDim.x on replica r's
+// weights, slabs, index and table.  The parameter struct is replica 0's and is read from
+// the kernel arguments as it is.  The *_table_* twins read the loss constants from
+// p.coef_table instead of the host values.
 __global__ __launch_bounds__(kThreads) void loss_grad_population_kernel(TrainParams p) {
   loss_grad_body<false, true>(p);
 }
@@ -49,7 +52,9 @@ struct AdamPopulationStep {
   float step_size[kMaxReplicas];   // lr[r] / (1 - beta1^t)
 };
 
-// slab_adam_kernel (train_run.hip: same order, same arithmetic) on replica blockIdx.y
+// slab_sum_kernel's sum (train.hip: same order, same arithmetic) on replica blockIdx.y,
+// then per index: Adam on the thread's weight, or the head mean to the log.  Plain vector
+// loads and stores.
 __global__ __launch_bounds__(kThreads) void slab_adam_population_kernel(AdamPopulationStep a) {
   const size_t r = blockIdx.y;
   const float* ws = a.ws + r * (size_t)a.blocks * a.stride;
@@ -101,8 +106,9 @@ struct ClipPopulation {
   float* table;            // [R][3][heads]: floor, coef_abs, coef_rel
 };
 
-// clip_kernel (train_run.hip, its arithmetic) with workgroup r on replica r's means and
-// table: the replicas clip independently
+// Trainer.loss_and_grad's host decision (training.py), in its arithmetic: a term whose
+// scaled mean (double) reaches error_max passes no gradient, so its coefficient is zero.
+// Workgroup r on replica r's means and table: the replicas clip independently.
 __global__ __launch_bounds__(64) void clip_population_kernel(ClipPopulation c) {
   const int i = threadIdx.x, H = c.heads;
   const float* head_means = c.head_means + (size_t)blockIdx.x * (2 * H);
@@ -121,7 +127,7 @@ static_assert(2 * kMaxUnrolledHeads <= 64, "clip_population_kernel: one thread p
 
 namespace {
 
-const void* population_kernel_entry(bool through_time, bool coef_table) {
+const void* population_loss_kernel(bool through_time, bool coef_table) {
   if (through_time)
     return coef_table
                ? reinterpret_cast<const void*>(unrolled_loss_grad_table_population_kernel)
@@ -142,9 +148,10 @@ hipError_t launch_train_population(const PopulationParams& pp, hipStream_t strea
   const int total = p.n_weights + 2 * r.heads;
   p.index_stride = pp.index_per_replica ? p.batch : 0;
   void* args[] = {through_time ? static_cast<void*>(&q) : static_cast<void*>(&p)};
-  const void* kernel = population_kernel_entry(through_time, clip);
+  const void* kernel = population_loss_kernel(through_time, clip);
   // (with clipping: the forward-only pass runs the kernel of the host values)
-  const void* forward = population_kernel_entry(through_time, false);
+  const void* forward = population_loss_kernel(through_time, false);
+  // the dynamic-LDS attribute once per kernel, not once per step
   hipError_t err = set_dynamic_lds(kernel, r.lds_bytes);
   if (err == hipSuccess && clip) err = set_dynamic_lds(forward, r.lds_bytes);
   if (err != hipSuccess) return err;

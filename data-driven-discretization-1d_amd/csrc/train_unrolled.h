@@ -47,9 +47,5 @@ __host__ __device__ inline size_t unrolled_lds_floats(const TrainParams& p) {
 hipError_t launch_unrolled_loss_grad(const UnrolledParams& q, int blocks, size_t lds_bytes,
                                      hipStream_t stream);
 
-// unrolled_loss_grad_kernel, or its twin that reads the loss constants from
-// q.t.coef_table, as launch_then_sum's `kernel` (train_run.hip)
-const void* unrolled_loss_grad_kernel_entry(bool coef_table);
-
 }  // namespace train
 }  // namespace ddd

@@ -25,21 +25,12 @@ __global__ __launch_bounds__(kThreads) void unrolled_loss_grad_kernel(UnrolledPa
   unrolled_loss_grad_body<false>(q);
 }
 
-__global__ __launch_bounds__(kThreads) void unrolled_loss_grad_table_kernel(UnrolledParams q) {
-  unrolled_loss_grad_body<true>(q);
-}
-
 hipError_t launch_unrolled_loss_grad(const UnrolledParams& q, int blocks, size_t lds_bytes,
                                      hipStream_t stream) {
   const TrainParams& p = q.t;
   return launch_then_sum(reinterpret_cast<const void*>(unrolled_loss_grad_kernel), &q, p, blocks,
                          lds_bytes, stream, p.want_grad ? 0 : p.n_weights,
                          p.n_weights + 2 * q.HT);
-}
-
-const void* unrolled_loss_grad_kernel_entry(bool coef_table) {
-  return coef_table ? reinterpret_cast<const void*>(unrolled_loss_grad_table_kernel)
-                    : reinterpret_cast<const void*>(unrolled_loss_grad_kernel);
 }
 
 }  // namespace train

@@ -1,6 +1,6 @@
 // The body of the training kernel through time (train_unrolled.h; the scheme is written
-// out at the top of train_unrolled.hip), shared by unrolled_loss_grad_kernel /
-// unrolled_loss_grad_table_kernel (train_unrolled.hip) and their replica forms
+// out at the top of train_unrolled.hip), shared by unrolled_loss_grad_kernel
+// (train_unrolled.hip) and the replica forms of the optimiser loop
 // (train_population.hip).  A workgroup is blockIdx.x of gridDim.x.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -7,11 +7,12 @@ Reference: training.py:168-189 (set_data_dependent_hparams), 358-417
 The optimiser is torch.optim.Adam(beta2=0.99) on the piecewise-constant schedule
 of learning_rates / learning_stops (training.py:191-218); the gradient comes from
 the kernel, not from autograd.  Trainer.run / training_loop(fused=True) hand a whole
-stretch of optimiser steps to the device in one call (ddd_train_run, csrc/train_run.hip:
-the same gradient with Adam fused into its slab sum, error_max decided on the device).
-PopulationTrainer / training_population train R replicas of one architecture -- R initial
-seeds, R learning-rate schedules -- in one such call (ddd_train_population_run,
-csrc/train_population.hip): the replicas are a second grid dimension of the same kernels.
+stretch of optimiser steps to the device in one call (ddd_train_run,
+csrc/train_population.hip: the same gradient with Adam fused into its slab sum, error_max
+decided on the device).  PopulationTrainer / training_population train R replicas of one
+architecture -- R initial seeds, R learning-rate schedules -- in one such call
+(ddd_train_population_run): the replicas are a second grid dimension of the same kernels,
+and ddd_train_run is the population of one.
 Inferer evaluates a trainer or a population over a whole dataset in one call
 (ddd_eval_metrics, csrc/train_metrics.hip) and returns the reference's calculate_metrics
 (training.py:433-491) per replica; training_loop / training_population(metrics=True) log

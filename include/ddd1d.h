@@ -585,8 +585,9 @@ typedef struct ddd_train_run_args {
   const int32_t* sample_index; /* device [num_steps][batch], required: step k trains
                                   on rows sample_index[k][0 .. batch-1].  An index
                                   outside [0, S) makes that step's logged means NaN
-                                  and, through the update, the weights, adam_m and
-                                  adam_v (ddd_train_loss_grad: head_means NaN). */
+                                  and, through the update (the gradient is NaN too),
+                                  the weights, adam_m and adam_v
+                                  (ddd_train_loss_grad: head_means NaN). */
   const float* labels;   /* [S][N][H'] */
   const float* baseline; /* [S][N][H'] */
   const double* learning_rate; /* HOST [num_steps], finite and >= 0 */

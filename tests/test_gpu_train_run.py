@@ -296,7 +296,50 @@ def test_one_step_through_time_is_exact():
   assert torch.isfinite(w).all() and not torch.equal(w, s['flat'])
 
 
-# ---- 7. training_loop(fused=True) ----
+# ---- 7. an index outside the dataset ----
+
+@pytest.mark.parametrize('num_time_steps', [0, 2])
+def test_bad_index_poisons_the_update(num_time_steps):
+  """An index outside [0, S) in step 0 (the solo mirror of test_replicas_are_isolated,
+  test_gpu_train_population.py): the kernel reads nothing for that sample; that step's
+  logged means, the gradient and, through the update, the weights and the Adam state
+  become NaN (the contract include/ddd1d.h states), and nothing behind them is touched."""
+  model = _model('burgers', False, 32, dict())
+  rows, batch, sentinel = 8, 4, -123.25
+  if num_time_steps:
+    s = _setup_unrolled(model, rows, num_time_steps, seed=4)
+    kwargs = dict(num_time_steps=num_time_steps, time_step=s['dt'])
+  else:
+    s = _setup(model, rows, seed=4)
+    kwargs = dict()
+  index = _index(2, batch, rows, seed=8)
+  index[0, 2] = rows   # out of range
+
+  def padded(t):   # a sentinel row behind the vector
+    return torch.stack([t, torch.full_like(t, sentinel)]).contiguous()
+  rs = np.random.RandomState(1)
+  w = padded(s['flat'])
+  m = padded(torch.as_tensor(1e-3 * rs.randn(s['flat'].numel()).astype(np.float32),
+                             device='cuda'))
+  v = padded(torch.as_tensor(rs.uniform(1e-6, 1e-5, s['flat'].numel()).astype(np.float32),
+                             device='cuda'))
+  log, last = _lib.train_run(
+      s['cfg'], w[0], m[0], v[0], s['y'], s['labels'], s['baseline'], index, [1e-3, 1e-3],
+      s['floor'], s['coef_abs'], s['coef_rel'], betas=BETAS, epsilon=EPS,
+      nullspace=s['nullspace'], bias=s['bias'], want_last_grad=True, **kwargs)
+  assert tuple(log.shape) == (2, 2, 3 + num_time_steps)
+  assert tuple(last.shape) == (s['flat'].numel(),)
+  print('NaN in log[0] {} of {}, in the weights {} of {}'.format(
+      int(torch.isnan(log[0]).sum()), log[0].numel(), int(torch.isnan(w[0]).sum()),
+      w.shape[1]))
+  assert torch.isnan(log[0]).all()
+  for t in (w[0], m[0], v[0], last):
+    assert torch.isnan(t).all()
+  for t in (w, m, v):
+    assert (t[1] == sentinel).all()
+
+
+# ---- 8. training_loop(fused=True) ----
 
 def test_training_loop_fused(tmp_path):
   """The shape of the reference's training_test: 100 random snapshots of 256 points,
