@@ -397,6 +397,9 @@ SIGNATURES = {
     'ddd_rollout_scores': (ctypes.c_int, [ctypes.POINTER(DDDRolloutScoresArgs), _V]),
     'ddd_population_create': (ctypes.c_int, [ctypes.POINTER(_V), ctypes.c_int,
                                              ctypes.POINTER(_V)]),
+    'ddd_population_create_replicated': (ctypes.c_int, [_V, ctypes.c_int, ctypes.POINTER(_V)]),
+    'ddd_population_load_weights': (ctypes.c_int, [_V, _V, ctypes.c_size_t, ctypes.c_int,
+                                                   ctypes.c_int, _V]),
     'ddd_population_destroy': (ctypes.c_int, [_V]),
     'ddd_population_integrate_adaptive_f64': (ctypes.c_int, [_V, _D, ctypes.c_int,
                                                              ctypes.c_double, ctypes.c_double,

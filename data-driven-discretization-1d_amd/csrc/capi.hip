@@ -24,6 +24,7 @@
 #include "launch.h"
 #include "launch_weno.h"
 #include "ops.h"
+#include "pack_device.h"
 #include "pack_weights.h"
 #ifdef DDD_PROBES
 #include "probe_kernels.h"
@@ -2682,6 +2683,8 @@ struct ddd_population {
   float* d_w_hidden = nullptr;
   float* d_w_final4 = nullptr;
   ddd::PopulationStrides strides{};   // (the weight strides; the output strides are per call)
+  ddd::packdev::Tables tables{};      // what ddd_population_load_weights packs by (model0's)
+  size_t n_weights = 0;               // floats of a replica's natural-layout weight vector
 };
 
 namespace {
@@ -2737,6 +2740,72 @@ int ddd_population_destroy(ddd_population* pop) {
   return DDD_OK;
 }
 
+namespace {
+
+// What a population asks of each of its models: a population form of both integrators
+// (whatever forcing the model carries now: the call plans again) and the three packed arrays.
+int check_population_model(const ddd_model* m, const char* who) {
+  Plan p;
+  int rc = plan_population(m, Op::adaptive, 1, &p, who);
+  if (!rc) rc = plan_population(m, Op::persistent, 1, &p, who);
+  if (rc) return rc;
+  if (m->d_w_input == nullptr || m->d_w_hidden == nullptr || m->d_w_final4 == nullptr ||
+      m->n_w_input != (size_t)ddd::packdev::kInputFloats ||
+      m->n_w_hidden != (size_t)ddd::packdev::kHiddenFloats ||
+      m->n_w_final4 != (size_t)ddd::packdev::kFinal4Floats)
+    return fail(DDD_ERR_UNSUPPORTED, "%s: packed weight arrays of other sizes than the "
+                "population kernels read", who);
+  return DDD_OK;
+}
+
+// The handle around model0 with room for `replicas` sets of packed weights (not yet filled).
+int new_population(ddd_model* m0, int replicas, ddd_population** out) {
+  ddd_population* pop = new ddd_population();
+  pop->model0 = m0;
+  pop->replicas = replicas;
+  pop->strides.w_input = (long long)m0->n_w_input;
+  pop->strides.w_hidden = (long long)m0->n_w_hidden;
+  pop->strides.w_final4 = (long long)m0->n_w_final4;
+  // ddd_population_load_weights: the tables of pack_device.h, model0's
+  const ddd::DevParams& dp = m0->dp;
+  ddd::packdev::Tables& t = pop->tables;
+  std::memcpy(t.ns8, dp.ns8, sizeof(t.ns8));
+  std::memcpy(t.bias8, dp.bias8, sizeof(t.bias8));
+  for (int d = 0; d < ddd::packdev::kDerivs; ++d) {
+    t.in_start[d] = dp.in_start[d];
+    t.in_size[d] = dp.in_size[d];
+  }
+  for (int l = 0; l < ddd::packdev::kLayers; ++l) { t.w_off[l] = dp.w_off[l]; t.b_off[l] = dp.b_off[l]; }
+  t.K = dp.K; t.F = dp.F; t.C_out = dp.C_out; t.D = dp.D; t.G = dp.G;
+  t.fin4_groups = dp.fin4_groups;
+  t.spec_folded = m0->spec_folded ? 1 : 0;
+  pop->n_weights = (size_t)dp.b_off[dp.L - 1] + (size_t)dp.cout[dp.L - 1];
+  const auto room = [&](float** dst, size_t n) -> int {
+    DDD_HIP(hipMalloc(reinterpret_cast<void**>(dst), (size_t)replicas * n * sizeof(float)));
+    return DDD_OK;
+  };
+  int rc = room(&pop->d_w_input, m0->n_w_input);
+  if (!rc) rc = room(&pop->d_w_hidden, m0->n_w_hidden);
+  if (!rc) rc = room(&pop->d_w_final4, m0->n_w_final4);
+  if (rc) { ddd_population_destroy(pop); return rc; }
+  *out = pop;
+  return DDD_OK;
+}
+
+// Replica r's three arrays = model m's, device to device (the caller synchronises).
+int copy_packed(ddd_population* pop, int r, const ddd_model* m) {
+  const auto copy = [&](float* dst, size_t n, const float* src) -> int {
+    DDD_HIP(hipMemcpy(dst + (size_t)r * n, src, n * sizeof(float), hipMemcpyDeviceToDevice));
+    return DDD_OK;
+  };
+  int rc = copy(pop->d_w_input, m->n_w_input, m->d_w_input);
+  if (!rc) rc = copy(pop->d_w_hidden, m->n_w_hidden, m->d_w_hidden);
+  if (!rc) rc = copy(pop->d_w_final4, m->n_w_final4, m->d_w_final4);
+  return rc;
+}
+
+}  // namespace
+
 int ddd_population_create(ddd_model* const* models, int replicas, ddd_population** out) {
   if (out == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "out is NULL");
   *out = nullptr;
@@ -2760,12 +2829,9 @@ int ddd_population_create(ddd_model* const* models, int replicas, ddd_population
   }
   for (int r = 0; r < replicas; ++r) {
     const ddd_model* m = models[r];
-    Plan p;
     char who[32];
     snprintf(who, sizeof(who), "models[%d]", r);
-    // (both integrators, whatever forcing the model carries now: the call plans again)
-    int rc = plan_population(m, Op::adaptive, 1, &p, who);
-    if (!rc) rc = plan_population(m, Op::persistent, 1, &p, who);
+    int rc = check_population_model(m, who);
     if (rc) return rc;
     const ddd::DevParams& a = m->dp;
     const ddd::DevParams& b = m0->dp;
@@ -2776,31 +2842,59 @@ int ddd_population_create(ddd_model* const* models, int replicas, ddd_population
       return fail(DDD_ERR_UNSUPPORTED,
                   "models[%d]: projection tables differ from models[0]'s (the replicas' "
                   "launch reads models[0]'s)", r);
-    if (m->n_w_input != m0->n_w_input || m->n_w_hidden != m0->n_w_hidden ||
-        m->n_w_final4 != m0->n_w_final4 || m->d_w_input == nullptr || m->d_w_hidden == nullptr ||
-        m->d_w_final4 == nullptr)
-      return fail(DDD_ERR_UNSUPPORTED, "models[%d]: packed weight arrays of other sizes than "
-                  "models[0]'s", r);
   }
-  ddd_population* pop = new ddd_population();
-  pop->model0 = models[0];
-  pop->replicas = replicas;
-  pop->strides.w_input = (long long)m0->n_w_input;
-  pop->strides.w_hidden = (long long)m0->n_w_hidden;
-  pop->strides.w_final4 = (long long)m0->n_w_final4;
-  const auto gather = [&](float** dst, size_t n, float* ddd_model::*src) -> int {
-    DDD_HIP(hipMalloc(reinterpret_cast<void**>(dst), (size_t)replicas * n * sizeof(float)));
-    for (int r = 0; r < replicas; ++r)
-      DDD_HIP(hipMemcpy(*dst + (size_t)r * n, models[r]->*src, n * sizeof(float),
-                        hipMemcpyDeviceToDevice));
-    return DDD_OK;
-  };
-  int rc = gather(&pop->d_w_input, m0->n_w_input, &ddd_model::d_w_input);
-  if (!rc) rc = gather(&pop->d_w_hidden, m0->n_w_hidden, &ddd_model::d_w_hidden);
-  if (!rc) rc = gather(&pop->d_w_final4, m0->n_w_final4, &ddd_model::d_w_final4);
+  ddd_population* pop = nullptr;
+  int rc = new_population(models[0], replicas, &pop);
+  if (rc) return rc;
+  for (int r = 0; r < replicas && !rc; ++r) rc = copy_packed(pop, r, models[r]);
   if (!rc) DDD_HIP(hipDeviceSynchronize());   // (the copies have read the models' arrays)
   if (rc) { ddd_population_destroy(pop); return rc; }
   *out = pop;
+  return DDD_OK;
+}
+
+int ddd_population_create_replicated(ddd_model* model, int replicas, ddd_population** out) {
+  if (out == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "out is NULL");
+  *out = nullptr;
+  if (model == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "model is NULL");
+  if (replicas < 1 || replicas > DDD_MAX_REPLICAS)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "replicas = %d outside [1, %d]", replicas,
+                DDD_MAX_REPLICAS);
+  int rc = check_population_model(model, "model");
+  if (rc) return rc;
+  ddd_population* pop = nullptr;
+  rc = new_population(model, replicas, &pop);
+  if (rc) return rc;
+  for (int r = 0; r < replicas && !rc; ++r) rc = copy_packed(pop, r, model);
+  if (!rc) DDD_HIP(hipDeviceSynchronize());
+  if (rc) { ddd_population_destroy(pop); return rc; }
+  *out = pop;
+  return DDD_OK;
+}
+
+int ddd_population_load_weights(ddd_population* pop, const float* weights, size_t n_weights,
+                                int first_replica, int count, void* stream) {
+  if (pop == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "population is NULL");
+  if (weights == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "weights is NULL");
+  if (first_replica < 0 || count < 0)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "first_replica = %d, count = %d: negative",
+                first_replica, count);
+  if (n_weights == 0) return fail(DDD_ERR_INVALID_ARGUMENT, "n_weights = 0");
+  if (count > pop->replicas - first_replica)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "replicas %d .. %d outside the population's 0 .. %d", first_replica,
+                first_replica + count - 1, pop->replicas - 1);
+  if (n_weights != pop->n_weights)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "n_weights = %zu, the model has %zu floats",
+                n_weights, pop->n_weights);
+  if (count == 0) return DDD_OK;
+  ddd::packdev::launch_pack(
+      pop->tables, weights, (long long)n_weights,
+      pop->d_w_input + (size_t)first_replica * ddd::packdev::kInputFloats,
+      pop->d_w_hidden + (size_t)first_replica * ddd::packdev::kHiddenFloats,
+      pop->d_w_final4 + (size_t)first_replica * ddd::packdev::kFinal4Floats, count,
+      static_cast<hipStream_t>(stream));
+  DDD_HIP(hipGetLastError());
   return DDD_OK;
 }
 

@@ -30,11 +30,14 @@ into one slab -- or, with ``launch='population'``, rolls all of them out in ONE 
 whose grid carries the replicas (``ddd_population_integrate_*``) -- and
 ``ddd_rollout_scores`` scores them in two launches; one small host read returns
 ``mae`` [replica, time_max, sample] and ``survival`` [replica,
-quantile, sample].
+quantile, sample].  A ``RolloutPopulation`` keeps the one-launch handle across calls and
+takes its replicas' weights from device tensors (``ddd_population_load_weights``), so a
+trained population is rolled out without its weights leaving the device.
 """
 import atexit
 import ctypes
 from typing import Dict, Optional, Sequence
+import weakref
 
 import numpy as np
 
@@ -321,6 +324,12 @@ def run_integrate_population(models: Sequence[model_lib.LearnedStencilModel], hp
   of it, because the library's rows are replica-major without row 0.  The handle and the
   models it references are released by the next population call whose launch has finished,
   by ``release_populations()``, or at interpreter exit.
+
+  ``models`` may instead be a ``RolloutPopulation``: a handle kept across calls whose
+  replicas were loaded from device tensors.  The rollout is then the one launch on the
+  current stream whatever ``launch`` and ``streams`` say, with no handle built, no device
+  synchronisation and no model handle per replica; the forcing is set on the population's
+  model; the tensors returned are what the list of the models with those weights gives.
   """
   if launch not in LAUNCHES:
     raise ValueError('launch must be one of {}, got {!r}'.format(LAUNCHES, launch))
@@ -328,6 +337,10 @@ def run_integrate_population(models: Sequence[model_lib.LearnedStencilModel], hp
   lib = _lib.load_library()
   if distributed.world_info()[2] > 1:
     raise RuntimeError('run_integrate_population runs on a single rank; shard with evaluate')
+  population = models if isinstance(models, RolloutPopulation) else None
+  if population is not None:
+    population._check_open()   # pylint: disable=protected-access
+    models = [population.model]
   models = list(models)
   if not models or len(set(id(m) for m in models)) != len(models):
     raise ValueError('models must be a non-empty sequence of distinct models')
@@ -357,16 +370,24 @@ def run_integrate_population(models: Sequence[model_lib.LearnedStencilModel], hp
     forcing = model_lib.forcing_from_equations(eqs)
     for model in models:
       model.set_forcing(forcing)
-  for model in models:
-    model._handle   # pylint: disable=pointless-statement,protected-access  (created here)
+  if population is None:
+    for model in models:
+      model._handle   # pylint: disable=pointless-statement,protected-access  (created here)
   # every buffer exists before the fork and is returned, so it outlives the join
-  shape = (len(models), len(times), samples, points)
+  replicas = len(models) if population is None else population.replicas
+  shape = (replicas, len(times), samples, points)
   y = torch.empty(shape, dtype=dtype, device=y0.device)
-  nfev = torch.zeros((len(models), samples), dtype=torch.int32, device=y0.device)
-  status = torch.zeros((len(models), samples), dtype=torch.int32, device=y0.device)
+  nfev = torch.zeros((replicas, samples), dtype=torch.int32, device=y0.device)
+  status = torch.zeros((replicas, samples), dtype=torch.int32, device=y0.device)
   if not adaptive:
     y[:, 0] = y0
     nfev.fill_(lib.ddd_scheme_stages(_lib.SCHEMES[scheme]) * num_steps)
+  if population is not None:   # the kept handle: nothing is built, nothing waits
+    _population_launch(lib, torch, population._handle, replicas, adaptive, y0, warmup + times,
+                       max_step, scheme, num_steps if not adaptive else 0,
+                       save_every if not adaptive else 1, y, nfev, status)
+    population._launched()   # pylint: disable=protected-access
+    return y, nfev, status
   if launch != 'streams':
     try:
       _population_rollout(lib, torch, models, adaptive, y0, warmup + times, max_step, scheme,
@@ -398,6 +419,8 @@ LAUNCHES = ('streams', 'population', 'auto')
 # population handles whose launch may still be running: (event recorded behind the launch,
 # handle, the models -- models[0] is read by the launch, the others only kept alive)
 _PENDING = []
+# the RolloutPopulations not yet closed (closed at interpreter exit, before the library goes)
+_OPEN = weakref.WeakSet()
 
 
 def _reap_populations(lib, wait: bool = False):
@@ -423,7 +446,16 @@ def release_populations():
       del _PENDING[:]
 
 
+def _close_rollout_populations():
+  for population in list(_OPEN):
+    try:
+      population.close()
+    except RuntimeError:   # (at exit: the device runtime may be gone before this runs)
+      pass
+
+
 atexit.register(release_populations)
+atexit.register(_close_rollout_populations)
 
 
 def _population_rollout(lib, torch, models, adaptive, y0, times, max_step, scheme, num_steps,
@@ -438,21 +470,8 @@ def _population_rollout(lib, torch, models, adaptive, y0, times, max_step, schem
   handle = ctypes.c_void_p()
   _lib.check_supported(lib.ddd_population_create(handles, len(models), ctypes.byref(handle)))
   try:
-    samples = int(y0.shape[0])
-    stream = _lib.current_stream()
-    if adaptive:
-      times = np.ascontiguousarray(times, dtype=np.float64)
-      _lib.check_supported(lib.ddd_population_integrate_adaptive_f64(
-          handle, times.ctypes.data_as(_lib._D), int(times.size), 1e-3, 1e-6, float(max_step),
-          0, y0.data_ptr(), y.data_ptr(), nfev.data_ptr(), status.data_ptr(), samples, stream))
-    else:
-      # (the library's rows are the saved states [replica, save, sample, x]; row 0 of y is y0)
-      saved = torch.empty((len(models), int(y.shape[1]) - 1) + tuple(y0.shape), dtype=y.dtype,
-                          device=y.device)
-      _lib.check_supported(lib.ddd_population_integrate_fixed(
-          handle, _lib.SCHEMES[scheme], float(times[0]), float(max_step), int(num_steps),
-          int(save_every), y0.data_ptr(), saved.data_ptr(), samples, stream))
-      y[:, 1:] = saved
+    _population_launch(lib, torch, handle, len(models), adaptive, y0, times, max_step, scheme,
+                       num_steps, save_every, y, nfev, status)
   except Exception:
     torch.cuda.current_stream().synchronize()
     lib.ddd_population_destroy(handle)
@@ -462,12 +481,120 @@ def _population_rollout(lib, torch, models, adaptive, y0, times, max_step, schem
   _PENDING.append((event, handle, list(models)))
 
 
+def _population_launch(lib, torch, handle, replicas, adaptive, y0, times, max_step, scheme,
+                       num_steps, save_every, y, nfev, status):
+  """The ddd_population_integrate_* call of population `handle` on the current stream."""
+  samples = int(y0.shape[0])
+  stream = _lib.current_stream()
+  if adaptive:
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    _lib.check_supported(lib.ddd_population_integrate_adaptive_f64(
+        handle, times.ctypes.data_as(_lib._D), int(times.size), 1e-3, 1e-6, float(max_step),
+        0, y0.data_ptr(), y.data_ptr(), nfev.data_ptr(), status.data_ptr(), samples, stream))
+  else:
+    # (the library's rows are the saved states [replica, save, sample, x]; row 0 of y is y0)
+    saved = torch.empty((replicas, int(y.shape[1]) - 1) + tuple(y0.shape), dtype=y.dtype,
+                        device=y.device)
+    _lib.check_supported(lib.ddd_population_integrate_fixed(
+        handle, _lib.SCHEMES[scheme], float(times[0]), float(max_step), int(num_steps),
+        int(save_every), y0.data_ptr(), saved.data_ptr(), samples, stream))
+    y[:, 1:] = saved
+
+
+class RolloutPopulation(object):
+  """A population handle kept across calls: room for ``replicas`` sets of packed weights of
+  ``model``'s architecture on the device (``ddd_population_create_replicated``), filled from
+  device tensors by ``load`` (``ddd_population_load_weights``: the device packer of
+  csrc/pack_device.hip, no host packing, no model handle per replica).  Pass it to
+  ``run_integrate_population`` / ``evaluate_population`` in place of the models: the
+  rollouts are then one launch on the current stream, and nothing is created, copied or
+  waited for per call.  ``model`` plays models[0] -- launch parameters, forcing,
+  projection tables -- and is kept alive here; until the first ``load`` every replica
+  holds ``model``'s own weights.  NotImplementedError, with the library's reason, where
+  there is no population kernel for ``model``.
+
+  Loads and rollouts are ordered by the stream they are enqueued on: use one stream, or
+  order the streams yourself."""
+
+  def __init__(self, model: model_lib.LearnedStencilModel, replicas: int):
+    _lib.require_gpu()
+    lib = _lib.load_library()
+    self.model = model
+    self.replicas = int(replicas)
+    self.n_weights = int(sum(w.size + b.size
+                             for w, b in zip(model.conv_kernels, model.conv_biases)))
+    self._event = None
+    self._handle = None
+    handle = ctypes.c_void_p()
+    _lib.check_supported(lib.ddd_population_create_replicated(
+        model._handle, self.replicas, ctypes.byref(handle)))   # pylint: disable=protected-access
+    self._handle = handle
+    _OPEN.add(self)
+
+  def _check_open(self):
+    if self._handle is None:
+      raise ValueError('this RolloutPopulation is closed')
+
+  def _launched(self):
+    """Records the event close() waits for, behind what was just enqueued."""
+    torch = _lib.require_gpu()
+    if self._event is None:
+      self._event = torch.cuda.Event()
+    self._event.record()
+
+  def load(self, weights, first_replica: int = 0):
+    """Replicas first_replica .. first_replica + count - 1 take ``weights``: a contiguous
+    float32 device tensor [count, n_weights] in ddd_model_create's layout (a Trainer's or
+    PopulationTrainer's ``weights``).  Enqueued on the current stream; ``weights`` must stay
+    unchanged until that work has run."""
+    torch = _lib.require_gpu()
+    self._check_open()
+    if (not isinstance(weights, torch.Tensor) or weights.device.type != 'cuda' or
+        weights.dtype != torch.float32 or weights.dim() != 2 or not weights.is_contiguous()):
+      raise ValueError('weights must be a contiguous float32 device tensor [count, n_weights]')
+    _lib.check(_lib.load_library().ddd_population_load_weights(
+        self._handle, weights.data_ptr(), int(weights.shape[1]), int(first_replica),
+        int(weights.shape[0]), _lib.current_stream()))
+    self._launched()
+    return self
+
+  def load_models(self, models: Sequence[model_lib.LearnedStencilModel], first_replica: int = 0):
+    """``load`` of the models' flat weights, stacked and uploaded."""
+    torch = _lib.require_gpu()
+    flat = np.stack([np.concatenate([np.concatenate([w.ravel(), b.ravel()])
+                                     for w, b in zip(m.conv_kernels, m.conv_biases)])
+                     for m in models]).astype(np.float32)
+    weights = torch.from_numpy(np.ascontiguousarray(flat)).cuda()
+    self.load(weights, first_replica)
+    # (the stream's caching allocator keeps `weights` whole until the load has run)
+    return self
+
+  def close(self):
+    """Waits for the last load or rollout enqueued through this object, then frees the
+    handle.  Also runs at interpreter exit (release_populations)."""
+    handle, self._handle = self._handle, None
+    if handle is None or _lib._lib is None:   # pylint: disable=protected-access
+      return
+    if self._event is not None:
+      self._event.synchronize()
+    _lib._lib.ddd_population_destroy(handle)   # pylint: disable=protected-access
+    _OPEN.discard(self)
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:  # pylint: disable=broad-except
+      pass
+
+
 def evaluate_population(models: Sequence[model_lib.LearnedStencilModel], hparams,
                         reference: RolloutReference, keep_trajectories: bool = False,
                         **kwargs):
   """``evaluate`` for R models at once (run_evaluation.py:181-216 per model): the
   rollouts of ``run_integrate_population`` (``kwargs``) from ``reference.y0``, scored by
   ``ddd_rollout_scores`` against ``reference``, then one host read.
+
+  ``models`` may be a ``RolloutPopulation`` (see run_integrate_population).
 
   Returns dict(mae [replica, time_max, sample], survival [replica, quantile, sample],
   num_evals [replica, sample], status [replica, sample], stop_times, quantiles) and,
@@ -489,9 +616,10 @@ def evaluate_population(models: Sequence[model_lib.LearnedStencilModel], hparams
              status=status.astype(np.int32), stop_times=np.asarray(reference.stop_times),
              quantiles=np.asarray(reference.quantiles))
   if keep_trajectories:
+    first = models.model if isinstance(models, RolloutPopulation) else models[0]
     out['samples'] = dict(
         y=y.permute(0, 2, 1, 3).contiguous().cpu().numpy(), time=time,
-        x=models[0].equation.grid.solution_x,
+        x=first.equation.grid.solution_x,
         sample=kwargs.get('first_seed', 0) + np.arange(reference.num_samples))
   return out
 

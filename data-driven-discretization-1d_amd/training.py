@@ -329,6 +329,7 @@ class PopulationTrainer(object):
     self.adam_m = torch.zeros_like(self.weights)
     self.adam_v = torch.zeros_like(self.weights)
     self.step_count = 0
+    self._rollout_population = None   # rollout_population()'s handle, built on first use
 
   @property
   def replicas(self) -> int:
@@ -387,6 +388,17 @@ class PopulationTrainer(object):
   def export(self) -> List[model_lib.LearnedStencilModel]:
     """The current weights as R LearnedStencilModels."""
     return [trainer.export() for trainer in self.trainers]
+
+  def rollout_population(self):
+    """The current weights as an evaluation.RolloutPopulation, without leaving the device:
+    the handle is built once, around models[0], and `weights` is packed into it again on
+    every call (ddd_population_load_weights, enqueued on the current stream).  What
+    evaluate_population makes of it is what it makes of export(), bit for bit.
+    NotImplementedError where the library has no population kernel for the models."""
+    from . import evaluation   # (evaluation does not import training)
+    if self._rollout_population is None:
+      self._rollout_population = evaluation.RolloutPopulation(self.models[0], self.replicas)
+    return self._rollout_population.load(self.weights)
 
 
 def _scaled_loss_per_head(sums, hparams) -> np.ndarray:
@@ -582,7 +594,8 @@ def rollout_metrics(result) -> List[Dict[str, float]]:
 def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], hparams,
                         init_seeds: Sequence[int], learning_rates=None, seed: int = 0,
                         num_steps: int = None, metrics: bool = False, select: str = None,
-                        rollout=None, rollout_launch: str = 'streams'):
+                        rollout=None, rollout_launch: str = 'streams',
+                        rollout_every: int = None):
   """training_loop(..., seed=seed, fused=True) for R replicas at once: the same dataset,
   train / validation split and minibatch order; replica r starts from
   LearnedStencilModel(coarse, hparams, init_seed=init_seeds[r]) and follows
@@ -601,7 +614,20 @@ def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], h
   rollout: an evaluation.RolloutReference; the exported models are then rolled out once
   after the last stretch (evaluation.evaluate_population) and the keys of rollout_metrics
   are added to every replica's last row, where select can name them.  rollout_launch is
-  evaluate_population's ``launch`` ('streams', 'population' or 'auto')."""
+  evaluate_population's ``launch`` ('streams', 'population' or 'auto').
+
+  rollout_every = k (with a rollout): the evaluations at steps that are multiples of k
+  (step 0 included) also roll the replicas out as they are then and add the same keys to
+  that row; the last row gets those of the final weights as before, with the same values as
+  under rollout_every=None.  Under rollout_launch 'population' or 'auto' these rollouts go
+  through PopulationTrainer.rollout_population(): the weights are packed on the device into
+  one handle kept for the whole run, with no export and no model handle per replica;
+  under 'streams', or where 'auto' finds no population kernel, by export() and the streams."""
+  if rollout_every is not None:
+    if rollout is None:
+      raise ValueError('rollout_every needs a rollout (an evaluation.RolloutReference)')
+    if int(rollout_every) != rollout_every or rollout_every < 1:
+      raise ValueError('rollout_every = {!r} (a positive number of steps)'.format(rollout_every))
   if len(checkpoint_dirs) != len(init_seeds):
     raise ValueError('one checkpoint directory per init seed')
   hparams = copy.deepcopy(hparams)
@@ -628,6 +654,25 @@ def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], h
     inferers = (Inferer(valid_data if valid_data.num_examples else train_eval, trainer),
                 Inferer(train_eval, trainer))
 
+  rolled_out_at = [None]   # the step whose weights the last rows' rollout keys are of
+
+  def roll_out(step):
+    """The rollout keys of the current weights into every replica's last row."""
+    from . import evaluation   # (evaluation does not import training)
+    scores = None
+    if rollout_launch != 'streams':
+      try:
+        scores = evaluation.evaluate_population(trainer.rollout_population(), hparams, rollout)
+      except NotImplementedError:
+        if rollout_launch == 'population':
+          raise
+    if scores is None:
+      scores = evaluation.evaluate_population(trainer.export(), hparams, rollout,
+                                              launch='streams')
+    for replica_rows, row in zip(rows, rollout_metrics(scores)):
+      replica_rows[-1].update(row)
+    rolled_out_at[0] = step
+
   def evaluate(step):
     data = valid_data if valid_data.num_examples else train_data
     logged = None
@@ -642,6 +687,8 @@ def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], h
         row.update(_metrics_row(step, logged[0][r], logged[1][r]))
         logging.info('replica %d: %s', r, metrics_one_linear(logged[0][r]))
       replica_rows.append(row)
+    if rollout_every is not None and step % rollout_every == 0:
+      roll_out(step)
 
   evaluate(0)
   batches = train_data.batch_indices()
@@ -657,7 +704,10 @@ def training_population(snapshots: np.ndarray, checkpoint_dirs: Sequence[str], h
   exported = trainer.export()
   for model, checkpoint_dir in zip(exported, checkpoint_dirs):
     model.save(checkpoint_dir)
-  if rollout is not None:
+  if rollout_every is not None:
+    if rolled_out_at[0] != steps:   # (the last evaluation was not one of them, or came earlier)
+      roll_out(steps)
+  elif rollout is not None:
     from . import evaluation   # (evaluation does not import training)
     scores = rollout_metrics(evaluation.evaluate_population(exported, hparams, rollout,
                                                             launch=rollout_launch))

@@ -866,6 +866,28 @@ DDD_API int ddd_population_integrate_fixed(ddd_population* population, int schem
     double dt, int n_steps, int save_every, const float* y0, float* y_out, int batch,
     void* stream);
 
+/* A population kept across calls, whose weights arrive from the device (for instance
+ * ddd_train_population_run's [R][n_weights] array): create it once with
+ * ddd_population_create_replicated, then ddd_population_load_weights before each rollout.
+ * No model handle per replica, no packing on the host, no synchronisation per call. */
+
+/* A population of `replicas` copies of `model`'s packed weights.  Same checks and plans as
+ * ddd_population_create on `replicas` models of model's architecture; `model` plays models[0]
+ * (launch parameters, forcing, projection tables) and must outlive the population. */
+DDD_API int ddd_population_create_replicated(ddd_model* model, int replicas, ddd_population** out);
+
+/* Packs `count` weight vectors in ddd_model_create's layout, DEVICE [count][n_weights], into
+ * replicas first_replica .. first_replica + count - 1, on `stream`: afterwards those replicas
+ * hold bit for bit what ddd_model_create + ddd_population_create would have given them.
+ * Enqueue only: no allocation, no copy to or from the host, no synchronisation.  Ordered
+ * against rollouts by stream order; loading while a rollout of this population runs on
+ * another stream is the caller's error.  Works on populations from either constructor.
+ * DDD_ERR_INVALID_ARGUMENT: NULL pointers, a range outside the population, an n_weights
+ * that is not the model's. */
+DDD_API int ddd_population_load_weights(ddd_population* population, const float* weights,
+                                        size_t n_weights, int first_replica, int count,
+                                        void* stream);
+
 /* ---- differentiable evaluation --------------------------------------------
  * Replaces: tf.gradients through model.predict_result (model.py:664-697), the
  * building block of the reference's differentiable time integration

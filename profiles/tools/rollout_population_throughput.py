@@ -13,18 +13,23 @@ versions alternated over `rounds` (at least 3) rounds:
   b  evaluate_population(streams=1)
   c  evaluate_population(streams=4)
   d  evaluate_population(launch='population'): all R rollouts in ONE launch, replicas on
-     the grid's second dimension (ddd_population_integrate_adaptive_f64)
+     the grid's second dimension (ddd_population_integrate_adaptive_f64); the handle is built
+     from R model handles for every call (R device-to-device copies, one device synchronise)
+  e  evaluate_population(RolloutPopulation): the same launch through a handle kept across
+     calls, its weights packed again from one [R, n_weights] device tensor on every call
+     (ddd_population_load_weights: what a trainer does between two stretches)
   s  scoring alone, on trajectories resident on the device: NumPy after a host copy
      against the two launches and their host read
 Every timing starts behind a device synchronise and ends behind one, by wall clock; the
 RolloutReference is built before the clock starts (it does not depend on the models).
 Medians and the spread (max - min) / median over the rounds are reported.
 
-  python profiles/tools/rollout_population_throughput.py [--rounds 3] [--versions abcsd]
+  python profiles/tools/rollout_population_throughput.py [--rounds 3] [--versions abcsde]
 
 --versions picks the versions that are alternated (a checkout from before version d
 existed is measured with its own copy of this tool: versions b and c there are the
-baseline of d here, profiles/rollout_population_one_launch.json).
+baseline of d here, profiles/rollout_population_one_launch.json; versions c and d of the
+checkout before version e are the baseline of profiles/rollout_population_persistent.json).
 """
 import argparse
 import json
@@ -81,6 +86,13 @@ def measure(version, replicas, repeats):
     call = lambda: evaluation.evaluate_population(models, hp, reference, streams=streams)
   elif version == 'd':
     call = lambda: evaluation.evaluate_population(models, hp, reference, launch='population')
+  elif version == 'e':
+    population = evaluation.RolloutPopulation(models[0], replicas)
+    weights = torch.from_numpy(np.stack([
+        np.concatenate([np.concatenate([w.ravel(), b.ravel()])
+                        for w, b in zip(m.conv_kernels, m.conv_biases)])
+        for m in models]).astype(np.float32)).cuda().contiguous()
+    call = lambda: evaluation.evaluate_population(population.load(weights), hp, reference)
   else:   # scoring alone: trajectories resident, (NumPy after a copy, the two launches)
     y, _, _ = evaluation.run_integrate_population(models, hp, reference.y0, TIMES)
     torch.cuda.synchronize()
@@ -121,7 +133,8 @@ def main():
   parser.add_argument('--rounds', type=int, default=3)
   parser.add_argument('--repeats', type=int, default=3, help='timed calls per child process')
   parser.add_argument('--replicas', type=int, nargs='*', default=REPLICAS)
-  parser.add_argument('--versions', default='abcsd', help='the versions alternated, of a b c s d')
+  parser.add_argument('--versions', default='abcsde',
+                      help='the versions alternated, of a b c s d e')
   parser.add_argument('--version', default=None, help='one version in this process (the children)')
   args = parser.parse_args()
   if args.version is not None:
