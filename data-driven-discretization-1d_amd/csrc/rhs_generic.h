@@ -129,8 +129,10 @@ __device__ __forceinline__ int wrap(int i, int n) {
 
 // dy[0..N) = finalize_time_derivative(t, predict_time_derivative(u[0..N)))
 // for the sample this workgroup owns.  u and dy live in LDS (c.u, c.dy).
-__device__ inline void eval_rhs(const DevParams& p, const Carve& c, long sample,
-                                float t, float* derivs_out, float* coeffs_out) {
+// (__forceinline__: left to the inliner it becomes a real call under rk23::solve_uniform,
+// with 1880 bytes of scratch per lane in adaptive_kernel)
+__device__ __forceinline__ void eval_rhs(const DevParams& p, const Carve& c, long sample,
+                                         float t, float* derivs_out, float* coeffs_out) {
   const int tid = threadIdx.x;
   const int n = p.N;
   const float* net = nullptr;   // [N][C_out]
@@ -390,12 +392,42 @@ __host__ __device__ inline size_t adaptive_lds_bytes(const DevParams& p) {
   return ((lds_bytes_with(p, 0, staged) + 15) & ~(size_t)15) + adaptive_extra_bytes(p);
 }
 
+// What adaptive_kernel hands to rk23::solve_uniform: the sample's state in LDS, thread
+// tid owning the points tid, tid + kThreads, ...
+struct AdaptiveBackend {
+  typedef float KT;
+  const DevParams& p;
+  const Carve& c;
+  long sample;
+  double* red;              // block_sum256's 4 doubles
+  double* y_out;            // row 0 of this sample
+  size_t row_stride;
+  int n, tid;
+  double *y, *y_new;
+  float *k0, *k1, *k2, *f;  // f = c.dy
+
+  template <typename F>
+  __device__ __forceinline__ void each(F fn) const {
+    for (int i = tid; i < n; i += kThreads) fn(i);
+  }
+  __device__ __forceinline__ void input(int i, double v) const { c.u[i] = (float)v; }
+  __device__ __forceinline__ void eval(double t) const {
+    __syncthreads();
+    eval_rhs(p, c, sample, (float)t, nullptr, nullptr);   // -> c.dy, ends with a barrier
+  }
+  __device__ __forceinline__ double sum(double part) const { return rk23::block_sum256(part, red); }
+  __device__ __forceinline__ void store(int row, int i, double v) const {
+    y_out[(size_t)row * row_stride + i] = v;
+  }
+  // c.dy / k / y are rewritten by the next trip
+  __device__ __forceinline__ void end_phase() const { __syncthreads(); }
+};
+
 // integrate.odeint (integrate.py:143-169) for a batch of samples on the generic
-// right-hand side: SciPy's RK23 (rk23.h) with one workgroup and one controller
-// per sample, float64 state and controller, float32 right-hand side with the
-// sample's own forcing.  Serves what the MFMA path does not carry -- first of
-// all the WENO5 + Godunov-flux "exact" Burgers solver (WENODifferentiator,
-// integrate.py:124-140) on its fine grid.
+// right-hand side: SciPy's RK23 (rk23::solve_uniform) with one workgroup and one
+// controller per sample, float64 state and controller, float32 right-hand side with
+// the sample's own forcing.  Serves what neither the MFMA kernels nor rhs_weno.h
+// carry: any net, any grid size.
 __global__ __launch_bounds__(kThreads) void adaptive_kernel(DevParams p, AdaptiveArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ double red[4];
@@ -411,113 +443,13 @@ __global__ __launch_bounds__(kThreads) void adaptive_kernel(DevParams p, Adaptiv
   const int n = p.N, tid = (int)threadIdx.x;
   const long sample = blockIdx.x;
   const size_t off = (size_t)sample * n;
-  const size_t row_stride = (size_t)a.batch * n;
   for (int i = tid; i < n; i += kThreads) { y[i] = a.y0[off + i]; y_new[i] = y[i]; }
   __syncthreads();
-
-  const double t0 = a.times[0];
-  const double t_bound = a.times[a.n_times - 1];
-  const double interval = fabs(t_bound - t0);
-  const double rtol = a.rtol, atol = a.atol, max_step = a.max_step;
-  const double sqrt_n = sqrt((double)n);
+  AdaptiveBackend b{p, c, sample, red, a.y_out + off, (size_t)a.batch * n, n, tid,
+                    y, y_new, k0, k1, k2, c.dy};
   rk23::Control ctl;
-  ctl.init(t0, true);
-  double h0 = 0.0, d1 = 0.0;
-  long long attempts = 0;
-  int phase = 0;
-  while (ctl.status == rk23::RUNNING) {   // uniform over the workgroup
-    double tt;
-    if (phase == 0) tt = ctl.t;
-    else if (phase == 1) tt = ctl.t + h0;
-    else if (phase == 2) tt = ctl.t + 0.5 * ctl.h;
-    else if (phase == 3) tt = ctl.t + 0.75 * ctl.h;
-    else tt = ctl.t + ctl.h;
-    for (int i = tid; i < n; i += kThreads) {
-      double yy;
-      if (phase == 0) yy = y[i];
-      else if (phase == 1) yy = y[i] + h0 * (double)k0[i];
-      else if (phase == 2) yy = rk23::stage2_input(y[i], k0[i], ctl.h);
-      else if (phase == 3) yy = rk23::stage3_input(y[i], k0[i], k1[i], ctl.h);
-      else yy = y_new[i];
-      c.u[i] = (float)yy;
-    }
-    __syncthreads();
-    eval_rhs(p, c, sample, (float)tt, nullptr, nullptr);   // -> c.dy, ends with a barrier
-    ++ctl.nfev;
-    double part = 0.0;
-    if (phase == 0) {
-      for (int i = tid; i < n; i += kThreads) k0[i] = c.dy[i];
-      if (a.n_times == 1) {
-        for (int i = tid; i < n; i += kThreads) a.y_out[off + i] = y[i];
-        ctl.ti = 1;
-        ctl.status = rk23::FINISHED;
-      } else {
-        for (int i = tid; i < n; i += kThreads) {
-          const double q = y[i] / (atol + fabs(y[i]) * rtol);
-          part += q * q;
-        }
-        const double d0 = sqrt(rk23::block_sum256(part, red)) / sqrt_n;
-        part = 0.0;
-        for (int i = tid; i < n; i += kThreads) {
-          const double q = (double)c.dy[i] / (atol + fabs(y[i]) * rtol);
-          part += q * q;
-        }
-        d1 = sqrt(rk23::block_sum256(part, red)) / sqrt_n;
-        h0 = rk23::Control::first_guess(d0, d1, interval);
-      }
-      phase = 1;
-    } else if (phase == 1) {
-      for (int i = tid; i < n; i += kThreads) {
-        const double q = (double)(c.dy[i] - k0[i]) / (atol + fabs(y[i]) * rtol);   // float32 difference
-        part += q * q;
-      }
-      const double d2 = sqrt(rk23::block_sum256(part, red)) / sqrt_n / h0;
-      ctl.initial_step(h0, d1, d2, interval, max_step);
-      ctl.begin_step(max_step);
-      ctl.begin_attempt(t_bound);
-      phase = 2;
-    } else if (phase == 2) {
-      for (int i = tid; i < n; i += kThreads) k1[i] = c.dy[i];
-      phase = 3;
-    } else if (phase == 3) {
-      for (int i = tid; i < n; i += kThreads) {
-        k2[i] = c.dy[i];
-        y_new[i] = rk23::new_state(y[i], k0[i], k1[i], k2[i], ctl.h);
-      }
-      phase = 4;
-    } else {
-      for (int i = tid; i < n; i += kThreads) {
-        const double q = rk23::scaled_error(y[i], y_new[i], k0[i], k1[i], k2[i], c.dy[i], ctl.h,
-                                            rtol, atol);
-        part += q * q;
-      }
-      const double error_norm = sqrt(rk23::block_sum256(part, red)) / sqrt_n;
-      if (ctl.error_test(error_norm)) {
-        while (ctl.ti < a.n_times) {
-          const double te = a.times[ctl.ti];
-          if (!(te <= ctl.t_new)) break;
-          const double x = (te - ctl.t) / ctl.h;
-          for (int i = tid; i < n; i += kThreads)
-            a.y_out[(size_t)ctl.ti * row_stride + off + i] =
-                rk23::dense_output(y[i], k0[i], k1[i], k2[i], c.dy[i], x, ctl.h);
-          ++ctl.ti;
-        }
-        for (int i = tid; i < n; i += kThreads) { y[i] = y_new[i]; k0[i] = c.dy[i]; }
-        ctl.advance(t_bound, max_step);
-      }
-      ++attempts;
-      if (ctl.status == rk23::RUNNING && attempts >= a.max_attempts)
-        ctl.status = rk23::ATTEMPT_LIMIT;
-      ctl.begin_attempt(t_bound);
-      phase = 2;
-    }
-    __syncthreads();   // c.dy / k / y are rewritten by the next iteration
-  }
-  if (ctl.status != rk23::FINISHED) {
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    for (int r = ctl.ti; r < a.n_times; ++r)
-      for (int i = tid; i < n; i += kThreads) a.y_out[(size_t)r * row_stride + off + i] = nan;
-  }
+  rk23::solve_uniform(b, ctl, a.times, a.n_times, a.rtol, a.atol, a.max_step, a.max_attempts,
+                      sqrt((double)n));
   if (tid == 0) {
     a.nfev[sample] = ctl.nfev;
     a.status[sample] = ctl.status;

@@ -244,6 +244,9 @@ __device__ __forceinline__ void eval_points(const Params& p, const double* __res
 // one workgroup and one controller per sample, kPts grid points per thread.
 // The equations of motion are autonomous and carry no forcing here (KdV / KS:
 // finalize_time_derivative is the identity, equations.py:417-419, 528-530).
+// The loop is rk23::solve_uniform's, kept as a hand copy: run through the shared driver
+// <1> fell from 6 to 5 workgroups per CU (121 -> 155 ms at 3 072 KS samples,
+// profiles/rk23_uniform_driver.txt).
 template <int kPts>
 __global__ __launch_bounds__(kThreads) void adaptive_kernel(Params p, AdaptiveArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem64[];

@@ -405,7 +405,9 @@ __global__ __launch_bounds__(64 * kWaves) void integrate_kernel(DevParams p, Int
 
 // ---- integrate.odeint (integrate.py:143-169) for a batch: SciPy's RK23 (rk23.h), one
 //      controller per sample = per wavefront, float64 state and controller, float32
-//      right-hand side; rhs_generic.h's adaptive_kernel statement by statement ----
+//      right-hand side; rk23::solve_uniform statement by statement, kept as a hand copy:
+//      run through the shared driver this kernel measured 2.6 % slower at N = 512 and
+//      lost a wavefront per SIMD at <2, KS> (profiles/rk23_uniform_driver.txt) ----
 template <int kP, int kEq>
 __global__ __launch_bounds__(64 * kWaves) void adaptive_kernel(DevParams p, AdaptiveArgs a) {
   __shared__ Shared sm;

@@ -1,13 +1,21 @@
-// SciPy's RK23 step-size controller (scipy/integrate/_ivp: RungeKutta.__init__,
-// select_initial_step, RungeKutta._step_impl, rk_step, RkDenseOutput), the part
-// that is per SAMPLE and scalar, shared by the three on-device adaptive
-// integrators:
+// SciPy's RK23 (scipy/integrate/_ivp: RungeKutta.__init__, select_initial_step,
+// RungeKutta._step_impl, rk_step, RkDenseOutput): the step-size controller, which is
+// per SAMPLE and scalar (Control), the per-grid-point formulas, and solve_uniform, the
+// loop that strings them together for one sample.  Shared by the four on-device
+// adaptive integrators:
 //   rhs_adaptive.h            learned / fixed stencils on the MFMA kernels, float32
-//                             right-hand side (SavedModelDifferentiator, integrate.py:48-71)
-//   rhs_generic.h             the generic kernel: WENO5 + Godunov "exact" Burgers solver
-//                             (WENODifferentiator, integrate.py:124-140), any other net
+//                             right-hand side (SavedModelDifferentiator, integrate.py:48-71);
+//                             several controllers per wavefront, so a loop of its own
+//   rhs_weno.h                WENO5 + Godunov "exact" Burgers solver (WENODifferentiator,
+//                             integrate.py:124-140), one wavefront per sample
+//   rhs_generic.h             the generic kernel: any other net or grid, one workgroup
+//                             per sample, state in LDS
 //   rhs_spectral.h            spectral "exact" solver, float64 right-hand side
 //                             (integrate.SpectralDifferentiator, integrate.py:108-121)
+// solve_uniform is the loop of the generic kernel and of the CPU tier's harness
+// (oracle/rk23_host.cpp).  The WENO and spectral kernels keep hand copies of it,
+// statement by statement: through the shared driver they lost occupancy and speed
+// (profiles/rk23_uniform_driver.txt).
 // Call site in the reference: integrate.odeint, integrate.py:154-155
 //   solve_ivp(differentiator, (t0, t1), y0, t_eval=times, max_step=0.01, method='RK23').
 // oracle/oracle.py::rk23_adaptive is the same restatement in NumPy, pinned
@@ -17,7 +25,8 @@
 #ifdef DDD_RK23_HOST
 // The same statements compiled by g++ for the CPU test tier
 // (oracle/rk23_host.cpp, tests/test_cpu_rk23_source.py): this very header,
-// driven over a Python right-hand side, against the installed SciPy.
+// solve_uniform included, driven over a Python right-hand side, against the
+// installed SciPy.
 #include <cmath>
 #include <cstring>
 #define __device__
@@ -208,6 +217,128 @@ __device__ __forceinline__ double dense_output(double y_old, KT k0, KT k1, KT k2
                      (double)k2 * (-8.0 / 9.0)) + (double)k3;
   const double x2 = x * x, x3 = x2 * x;
   return h * (((double)k0 * x + q1 * x2) + q2 * x3) + y_old;
+}
+
+// ---- the solve, for a UNIFORM controller: one sample, one Control shared by every
+//      thread that holds some of its points (rhs_generic.h, oracle/rk23_host.cpp; the
+//      loops of rhs_weno.h and rhs_spectral.h are hand copies of this one; rhs_adaptive.h
+//      packs per-sample controllers into a shared wavefront and is a different machine) ----
+// solve_ivp from f(y0) to the NaN rows of a sample that did not finish, as one loop with
+// ONE evaluation per trip: f(y0), select_initial_step's probe, stages 2 and 3, the FSAL
+// stage with the error test and the dense output.  B, the caller's backend:
+//   B::KT                    type of the right-hand side's values
+//   each(fn)                 fn(i) for the point slots this thread owns, in slot order
+//   y[i], y_new[i]           double; k0[i], k1[i], k2[i], f[i]: KT, f = the last evaluation
+//   input(i, v)              the right-hand side's argument at slot i
+//   eval(t)                  f = right-hand side of the inputs, by all threads
+//   sum(part)                the sample's total of the threads' parts, the same bits on each
+//   store(row, i, v)         y_out
+//   end_phase()              after every trip (a barrier where slots live in shared memory)
+// Every thread adds its terms in slot order into one partial sum.
+template <typename B>
+__device__ __forceinline__ void solve_uniform(B& b, Control& ctl, const double* times, int n_times,
+                                              double rtol, double atol, double max_step,
+                                              long long max_attempts,   // > 0: the caller maps
+                                                                        // "no limit" to a number
+                                              double sqrt_n) {
+  typedef typename B::KT KT;
+  const double t0 = times[0];
+  const double t_bound = times[n_times - 1];
+  const double interval = fabs(t_bound - t0);
+  ctl.init(t0, true);
+  double h0 = 0.0, d1 = 0.0;
+  long long attempts = 0;
+  int phase = 0;
+  while (ctl.status == RUNNING) {   // uniform over the sample's threads
+    double tt;
+    if (phase == 0) tt = ctl.t;
+    else if (phase == 1) tt = ctl.t + h0;
+    else if (phase == 2) tt = ctl.t + 0.5 * ctl.h;
+    else if (phase == 3) tt = ctl.t + 0.75 * ctl.h;
+    else tt = ctl.t + ctl.h;
+    b.each([&](int i) {
+      double yy;
+      if (phase == 0) yy = b.y[i];
+      else if (phase == 1) yy = b.y[i] + h0 * (double)b.k0[i];
+      else if (phase == 2) yy = stage2_input(b.y[i], b.k0[i], ctl.h);
+      else if (phase == 3) yy = stage3_input(b.y[i], b.k0[i], b.k1[i], ctl.h);
+      else yy = b.y_new[i];
+      b.input(i, yy);
+    });
+    b.eval(tt);
+    ++ctl.nfev;
+    double part = 0.0;
+    if (phase == 0) {
+      b.each([&](int i) { b.k0[i] = b.f[i]; });
+      if (n_times == 1) {
+        b.each([&](int i) { b.store(0, i, b.y[i]); });
+        ctl.ti = 1;
+        ctl.status = FINISHED;
+      } else {
+        b.each([&](int i) {
+          const double q = b.y[i] / (atol + fabs(b.y[i]) * rtol);
+          part += q * q;
+        });
+        const double d0 = sqrt(b.sum(part)) / sqrt_n;
+        part = 0.0;
+        b.each([&](int i) {
+          const double q = (double)b.k0[i] / (atol + fabs(b.y[i]) * rtol);
+          part += q * q;
+        });
+        d1 = sqrt(b.sum(part)) / sqrt_n;
+        h0 = Control::first_guess(d0, d1, interval);
+      }
+      phase = 1;
+    } else if (phase == 1) {
+      b.each([&](int i) {   // the difference in the right-hand side's own type
+        const double q = (double)(KT)(b.f[i] - b.k0[i]) / (atol + fabs(b.y[i]) * rtol);
+        part += q * q;
+      });
+      const double d2 = sqrt(b.sum(part)) / sqrt_n / h0;
+      ctl.initial_step(h0, d1, d2, interval, max_step);
+      ctl.begin_step(max_step);
+      ctl.begin_attempt(t_bound);
+      phase = 2;
+    } else if (phase == 2) {
+      b.each([&](int i) { b.k1[i] = b.f[i]; });
+      phase = 3;
+    } else if (phase == 3) {
+      b.each([&](int i) {
+        b.k2[i] = b.f[i];
+        b.y_new[i] = new_state(b.y[i], b.k0[i], b.k1[i], b.k2[i], ctl.h);
+      });
+      phase = 4;
+    } else {
+      b.each([&](int i) {
+        const double q = scaled_error(b.y[i], b.y_new[i], b.k0[i], b.k1[i], b.k2[i], b.f[i],
+                                      ctl.h, rtol, atol);
+        part += q * q;
+      });
+      const double error_norm = sqrt(b.sum(part)) / sqrt_n;
+      if (ctl.error_test(error_norm)) {
+        while (ctl.ti < n_times) {
+          const double te = times[ctl.ti];
+          if (!(te <= ctl.t_new)) break;
+          const double x = (te - ctl.t) / ctl.h;
+          b.each([&](int i) {
+            b.store(ctl.ti, i, dense_output(b.y[i], b.k0[i], b.k1[i], b.k2[i], b.f[i], x, ctl.h));
+          });
+          ++ctl.ti;
+        }
+        b.each([&](int i) { b.y[i] = b.y_new[i]; b.k0[i] = b.f[i]; });
+        ctl.advance(t_bound, max_step);
+      }
+      ++attempts;
+      if (ctl.status == RUNNING && attempts >= max_attempts) ctl.status = ATTEMPT_LIMIT;
+      ctl.begin_attempt(t_bound);
+      phase = 2;
+    }
+    b.end_phase();
+  }
+  if (ctl.status != FINISHED) {
+    const double nan = double_of(0x7ff8000000000000ll);
+    for (int r = ctl.ti; r < n_times; ++r) b.each([&](int i) { b.store(r, i, nan); });
+  }
 }
 
 }  // namespace rk23

@@ -1,9 +1,12 @@
-"""The product's RK23 controller SOURCE (csrc/rk23.h: the per-sample controller
-and per-grid-point formulas shared by rhs_adaptive.h, rhs_generic.h and
-rhs_spectral.h) compiled for the CPU (oracle/rk23_host.cpp, g++) and driven over
-Python right-hand sides, against the installed SciPy -- the reference's
-integrator (integrate.py:154-155: solve_ivp(..., max_step=0.01, method='RK23')).
-No GPU: this pins the statements the kernels execute, not a twin of them."""
+"""The product's RK23 SOURCE (csrc/rk23.h: the per-sample controller and
+per-grid-point formulas shared by every adaptive kernel, and rk23::solve_uniform,
+the loop the generic kernel runs) compiled for the CPU (oracle/rk23_host.cpp, g++:
+a one-thread backend over that same loop) and driven over Python right-hand sides,
+against the installed SciPy -- the reference's integrator (integrate.py:154-155:
+solve_ivp(..., max_step=0.01, method='RK23')).
+No GPU: this pins the statements the generic kernel executes, not a twin of them
+(the WENO and spectral kernels keep hand copies of the loop; the GPU tier checks
+those)."""
 import ctypes
 import os
 import subprocess

@@ -12,7 +12,7 @@ import pytest
 
 from helpers import (FLOOR_CEILING, assert_near_truth, batch_forcing, make_model, oracle,
                      random_phase_ic, rel_err)
-from ddd1d_amd import integrate, model as model_lib
+from ddd1d_amd import equations, integrate, model as model_lib
 
 pytestmark = pytest.mark.gpu
 
@@ -299,6 +299,16 @@ def test_attempt_limit_and_argument_checks():
   # a single output time: nothing to integrate, one evaluation (RungeKutta.__init__)
   y, nfev, status = model.integrate_adaptive(y0, [0.25])
   assert np.array_equal(y[0].cpu().numpy(), y0) and (nfev.cpu().numpy() == 1).all()
+  # the same two corners on the spectral kernel (float64 right-hand side)
+  eq = equations.KdVEquation(64, random_seed=1)
+  spectral = model_lib.SpectralModel(eq)
+  y0 = random_phase_ic(eq, 3).astype(np.float64)
+  y, nfev, status = spectral.integrate_adaptive(y0, [0.0, 1.0], max_attempts=5)
+  assert (status.cpu().numpy() == -2).all() and (nfev.cpu().numpy() == 2 + 3 * 5).all()
+  assert np.isnan(y[1].cpu().numpy()).all() and np.array_equal(y[0].cpu().numpy(), y0)
+  y, nfev, status = spectral.integrate_adaptive(y0, [0.25])
+  assert np.array_equal(y[0].cpu().numpy(), y0) and (nfev.cpu().numpy() == 1).all()
+  assert (status.cpu().numpy() == 0).all()
 
 def test_generic_kernel_models():
   """Nets the MFMA path does not carry (here kernel_size = 9, filter_size = 96) and the WENO5

@@ -376,18 +376,31 @@ def test_integrate_exact_batch_weno_burgers(monkeypatch):
 
 
 def test_spectral_adaptive_large_grid_and_failure(monkeypatch):
-  """N = 512 (two grid points per thread) and N = 2048 (eight); a sample that
-  blows up stops with status -1 and NaN rows while its neighbours finish."""
+  """N = 512 (two grid points per thread), N = 1024 (four) and N = 2048 (eight); a
+  sample that blows up stops with status -1 and NaN rows while its neighbours finish.
+  On these smooth initial values the controller takes each horizon in ONE step at the
+  reference's max_step = 0.01 (5 evaluations).  The N = 1024 entry therefore runs with
+  max_step = 1e-6, below the RK23 stability limit of u_xxx on dx = 1/32
+  (sqrt(3) / k_max^3 = 1.7e-6): a saturated controller, 201 steps and 605 evaluations
+  per sample, so that FSAL carries k0 from step to step and the three output rows come
+  from different steps."""
+  import scipy.integrate
   monkeypatch.setattr(integrate, 'DEVICE_ODEINT', False)
-  for n, horizon in ((512, 2e-3), (2048, 2e-5)):
+  for n, horizon, max_step in ((512, 2e-3, 0.01), (1024, 2e-4, 1e-6), (2048, 2e-5, 0.01)):
     eq = equations.KdVEquation(n, random_seed=3)
     model = model_lib.SpectralModel(eq)
     y0 = np.stack([eq.initial_value(), 0.5 * eq.initial_value()])
     times = np.linspace(0, horizon, 3)
-    y, nfev, status = model.integrate_adaptive(y0, times)
+    y, nfev, status = model.integrate_adaptive(y0, times, max_step=max_step)
     diff = integrate.SpectralDifferentiator(eq)
     for b in range(2):
-      want, want_nfev = integrate.odeint(y0[b], diff, times)
+      if max_step == 0.01:
+        want, want_nfev = integrate.odeint(y0[b], diff, times)
+      else:   # the same solve_ivp call as integrate.odeint's, with this max_step
+        sol = scipy.integrate.solve_ivp(diff, (times[0], times[-1]), y0[b], t_eval=times,
+                                        max_step=max_step, method='RK23')
+        want, want_nfev = sol.y.T, sol.nfev
+        assert want_nfev > 300, want_nfev
       assert int(nfev[b]) == want_nfev and int(status[b]) == 0, (n, b, int(nfev[b]), want_nfev)
       assert rel_err(y[:, b].cpu().numpy(), want) < 1e-9
 
