@@ -376,8 +376,9 @@ def test_integrate_exact_batch_weno_burgers(monkeypatch):
 
 
 def test_spectral_adaptive_large_grid_and_failure(monkeypatch):
-  """N = 512 (two grid points per thread), N = 1024 (four) and N = 2048 (eight); a
-  sample that blows up stops with status -1 and NaN rows while its neighbours finish.
+  """N = 512 (two grid points per thread), N = 1024 (four) and N = 2048 (eight).  (The
+  failure path -- status -1 and NaN rows next to samples that finish -- is
+  test_gpu_spectral_kernels.py::test_adaptive_failure_between_healthy_samples.)
   On these smooth initial values the controller takes each horizon in ONE step at the
   reference's max_step = 0.01 (5 evaluations).  The N = 1024 entry therefore runs with
   max_step = 1e-6, below the RK23 stability limit of u_xxx on dx = 1/32
