@@ -111,6 +111,41 @@ class DDDTrainUnrolledArgs(ctypes.Structure):
   ]
 
 
+MAX_ROLLOUT_STEPS = 256   # DDD_MAX_ROLLOUT_STEPS
+
+
+class DDDTrainRolloutArgs(ctypes.Structure):
+  """struct ddd_train_rollout_args."""
+  _fields_ = [
+      ('struct_size', ctypes.c_int32),
+      ('batch', ctypes.c_int32),
+      ('num_rows', ctypes.c_int32),
+      ('num_steps', ctypes.c_int32),
+      ('save_every', ctypes.c_int32),
+      ('weights', ctypes.c_void_p),
+      ('nullspace', ctypes.c_void_p),
+      ('bias', ctypes.c_void_p),
+      ('y0', ctypes.c_void_p),
+      ('sample_index', ctypes.c_void_p),
+      ('targets', ctypes.c_void_p),
+      ('step_weights', ctypes.c_void_p),
+      ('dt', ctypes.c_double),
+      ('t0', ctypes.c_void_p),
+      ('nparams', ctypes.c_int32),
+      ('n_k', ctypes.c_int32),
+      ('amplitude', ctypes.c_void_p),
+      ('omega', ctypes.c_void_p),
+      ('phase', ctypes.c_void_p),
+      ('k_index', ctypes.c_void_p),
+      ('spatial_phase', ctypes.c_void_p),
+      ('step_means', ctypes.c_void_p),
+      ('grad', ctypes.c_void_p),
+      ('trajectory', ctypes.c_void_p),
+      ('workspace', ctypes.c_void_p),
+      ('workspace_bytes', ctypes.c_size_t),
+  ]
+
+
 class DDDTrainRunArgs(ctypes.Structure):
   """struct ddd_train_run_args."""
   _fields_ = [
@@ -377,6 +412,11 @@ SIGNATURES = {
     'ddd_train_unrolled_loss_grad': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
                                                     ctypes.POINTER(DDDTrainUnrolledArgs),
                                                     _V]),
+    'ddd_train_rollout_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(DDDConfig),
+                                                             ctypes.c_int, ctypes.c_int]),
+    'ddd_train_rollout_loss_grad': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
+                                                   ctypes.POINTER(DDDTrainRolloutArgs),
+                                                   _V]),
     'ddd_train_run_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(DDDConfig),
                                                          ctypes.c_int, ctypes.c_int]),
     'ddd_train_run': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
@@ -708,6 +748,87 @@ def train_unrolled_loss_grad(cfg, weights, y, labels, baseline, error_floor, coe
       lambda b: lib.ddd_train_unrolled_workspace_bytes(ctypes.byref(cfg), b, steps),
       args, steps, cfg, weights, y, labels, baseline, error_floor, coef_abs, coef_rel,
       nullspace, bias, sample_index, batch, want_grad, want_predictions, workspace)
+
+
+def train_rollout_loss_grad(cfg, weights, y0, targets, step_weights, num_steps, save_every,
+                            dt, t0=None, forcing=None, nullspace=None, bias=None,
+                            sample_index=None, batch=None, want_grad=True,
+                            want_trajectory=False, workspace=None):
+  """ddd_train_rollout_loss_grad: (step_means [T / save_every], grad or None, trajectory
+  [batch, T / save_every, N] or None).
+
+  weights / y0 [S, N] / targets [S, T / save_every, N] / step_weights [T / save_every] /
+  nullspace / bias are float32 device tensors, t0 a float64 device tensor [S] or None (0),
+  sample_index an int32 device tensor [batch] or None (rows 0..batch-1).  forcing: None
+  (unforced) or a dict of device tensors with one row per row of y0 -- amplitude, omega,
+  phase float32 [S, P], k_index int32 [S, P], spatial_phase float32 [n_k, N]
+  (model.forcing_kernel_tables' keys).  `workspace`: a uint8 device tensor of at least
+  ddd_train_rollout_workspace_bytes bytes, reused across calls when given."""
+  lib = load_library()
+  torch = require_gpu()
+  steps, every = int(num_steps), int(save_every)
+  if every < 1 or steps < 1 or steps % every:
+    raise ValueError('save_every = {} must be >= 1 and divide num_steps = {}'.format(
+        every, steps))
+  saved = steps // every
+  if batch is None:
+    batch = int(sample_index.shape[0]) if sample_index is not None else int(y0.shape[0])
+  if y0.dim() != 2 or y0.shape[1] != cfg.num_points:
+    raise ValueError('expected y0 [S, N]')
+  rows, n = int(y0.shape[0]), int(y0.shape[1])
+  _check_f32_device('weights', weights, (vjp_num_weights(cfg),))
+  _check_f32_device('y0', y0, (rows, n))
+  _check_f32_device('targets', targets, (rows, saved, n))
+  _check_f32_device('step_weights', step_weights, (saved,))
+  for name, tensor in (('nullspace', nullspace), ('bias', bias)):
+    if tensor is not None:
+      _check_f32_device(name, tensor, tuple(tensor.shape))
+  if t0 is not None:
+    _check_device('t0', t0, torch.float64, (rows,))
+  if sample_index is not None:
+    _check_device('sample_index', sample_index, torch.int32, (int(batch),))
+  args = DDDTrainRolloutArgs()
+  if forcing is not None:
+    nparams = int(forcing['amplitude'].shape[1])
+    n_k = int(forcing['spatial_phase'].shape[0])
+    for name in ('amplitude', 'omega', 'phase'):
+      _check_f32_device(name, forcing[name], (rows, nparams))
+    _check_device('k_index', forcing['k_index'], torch.int32, (rows, nparams))
+    _check_f32_device('spatial_phase', forcing['spatial_phase'], (n_k, n))
+    args.nparams, args.n_k = nparams, n_k
+    for name in ('amplitude', 'omega', 'phase', 'k_index', 'spatial_phase'):
+      setattr(args, name, forcing[name].data_ptr())
+  ws_bytes = lib.ddd_train_rollout_workspace_bytes(ctypes.byref(cfg), int(batch), steps)
+  if ws_bytes == 0:
+    check(-1)
+  if workspace is None or workspace.numel() < ws_bytes:
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y0.device)
+  step_means = torch.empty((saved,), dtype=torch.float32, device=y0.device)
+  grad = torch.empty_like(weights) if want_grad else None
+  trajectory = (torch.empty((int(batch), saved, n), dtype=torch.float32, device=y0.device)
+                if want_trajectory else None)
+  args.struct_size = ctypes.sizeof(args)
+  args.batch = int(batch)
+  args.num_rows = rows
+  args.num_steps = steps
+  args.save_every = every
+  args.weights = weights.data_ptr()
+  args.nullspace = None if nullspace is None else nullspace.data_ptr()
+  args.bias = None if bias is None else bias.data_ptr()
+  args.y0 = y0.data_ptr()
+  args.sample_index = None if sample_index is None else sample_index.data_ptr()
+  args.targets = targets.data_ptr()
+  args.step_weights = step_weights.data_ptr()
+  args.dt = float(dt)
+  args.t0 = None if t0 is None else t0.data_ptr()
+  args.step_means = step_means.data_ptr()
+  args.grad = None if grad is None else grad.data_ptr()
+  args.trajectory = None if trajectory is None else trajectory.data_ptr()
+  args.workspace = workspace.data_ptr()
+  args.workspace_bytes = workspace.numel()
+  check(lib.ddd_train_rollout_loss_grad(ctypes.byref(cfg), ctypes.byref(args),
+                                        current_stream()))
+  return step_means, grad, trajectory
 
 
 def _check_training_data(cfg, steps, y, labels, baseline, nullspace, bias):

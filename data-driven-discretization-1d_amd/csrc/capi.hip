@@ -39,6 +39,7 @@
 #include "train.h"
 #include "train_metrics.h"
 #include "train_population.h"
+#include "train_rollout.h"
 #include "train_unrolled.h"
 #include "rhs_weno.h"   // (host side only: weno::supports; the kernels are weno_unit.hip)
 
@@ -1499,6 +1500,44 @@ int train_unrolled_params(const ddd_config* cfg, int batch, int num_time_steps,
   up->st_off = (int)((size_t)p.n_slab + z_floats);
   up->gi_off = up->st_off + 2 * T * p.N;
   p.slab_stride = ((size_t)up->gi_off + (size_t)T * p.N + 3) & ~(size_t)3;
+  *ws_bytes = (size_t)*blocks * p.slab_stride * sizeof(float);
+  if (p.mfma && ddd::train::unrolled_lds_floats(p) * sizeof(float) > 160 * 1024) {
+    p.mfma = 0;
+    p.wl_floats = 0;
+    for (int l = 0; l < p.L; ++l) p.wl_off[l] = -1;
+  }
+  *lds_bytes = ddd::train::unrolled_lds_floats(p) * sizeof(float);
+  if (*lds_bytes > 160 * 1024)
+    return fail(DDD_ERR_UNSUPPORTED, "%s: %zu bytes of LDS needed (> 160 KiB)", who,
+                *lds_bytes);
+  return DDD_OK;
+}
+
+static_assert(ddd::train::kMaxRolloutSteps == DDD_MAX_ROLLOUT_STEPS, "train_rollout.h / ddd1d.h");
+
+// train_params for ddd_train_rollout_loss_grad (train_rollout.h) under that name: the
+// same checks and messages, then num_steps.  A slab is laid out for save_every = 1 (the
+// workspace function does not know it): num_steps sums behind the gradient, then the
+// pre-activations, the 2 T stage states and up to T saved-step cotangents.  The LDS plan
+// and its 160 KiB check are train_unrolled_params'.
+int train_rollout_params(const ddd_config* cfg, int batch, int num_steps,
+                         ddd::train::RolloutParams* rp, int* blocks, size_t* ws_bytes,
+                         size_t* lds_bytes) {
+  const char* who = "ddd_train_rollout_loss_grad";
+  std::memset(rp, 0, sizeof(*rp));
+  ddd::train::TrainParams& p = rp->t;
+  int rc = train_params(cfg, batch, &p, blocks, ws_bytes, lds_bytes, who);
+  if (rc) return rc;
+  if (num_steps < 1 || num_steps > DDD_MAX_ROLLOUT_STEPS)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "%s: num_steps = %d out of range [1, %d]", who,
+                num_steps, DDD_MAX_ROLLOUT_STEPS);
+  const int T = num_steps;
+  rp->T = T;
+  const size_t z_floats = p.slab_stride - (size_t)p.n_slab;
+  p.n_slab = (int)(((size_t)p.n_weights + T + 3) & ~(size_t)3);
+  rp->st_off = (int)((size_t)p.n_slab + z_floats);
+  rp->gi_off = rp->st_off + 2 * T * p.N;
+  p.slab_stride = ((size_t)rp->gi_off + (size_t)T * p.N + 3) & ~(size_t)3;
   *ws_bytes = (size_t)*blocks * p.slab_stride * sizeof(float);
   if (p.mfma && ddd::train::unrolled_lds_floats(p) * sizeof(float) > 160 * 1024) {
     p.mfma = 0;
@@ -3133,6 +3172,86 @@ int ddd_train_unrolled_loss_grad(const ddd_config* cfg, const ddd_train_unrolled
   if (rc) return rc;
   q.dt = a->time_step;
   DDD_HIP(ddd::train::launch_unrolled_loss_grad(q, blocks, lds, static_cast<hipStream_t>(stream)));
+  return DDD_OK;
+}
+
+size_t ddd_train_rollout_workspace_bytes(const ddd_config* cfg, int batch, int num_steps) {
+  ddd::train::RolloutParams q;
+  int blocks = 0;
+  size_t ws = 0, lds = 0;
+  if (train_rollout_params(cfg, batch, num_steps, &q, &blocks, &ws, &lds)) return 0;
+  return ws;
+}
+
+int ddd_train_rollout_loss_grad(const ddd_config* cfg, const ddd_train_rollout_args* a,
+                                void* stream) {
+  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
+  if (a->struct_size != (int32_t)sizeof(ddd_train_rollout_args))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_train_rollout_args.struct_size = %d, library expects %d (ABI mismatch)",
+                a->struct_size, (int)sizeof(ddd_train_rollout_args));
+  ddd::train::RolloutParams q;
+  ddd::train::TrainParams& p = q.t;
+  int blocks = 0;
+  size_t ws = 0, lds = 0;
+  int rc = train_rollout_params(cfg, a->batch, a->num_steps, &q, &blocks, &ws, &lds);
+  if (rc) return rc;
+  if (a->save_every < 1 || a->num_steps % a->save_every != 0)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "save_every = %d must be >= 1 and divide num_steps = %d",
+                a->save_every, a->num_steps);
+  if (!(a->dt > 0.0) || !std::isfinite(a->dt))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "dt = %g must be positive and finite", a->dt);
+  if (!a->weights || !a->y0 || !a->targets || !a->step_weights || !a->step_means)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "weights, y0, targets, step_weights and step_means must not be NULL");
+  const int tables = (a->amplitude != nullptr) + (a->omega != nullptr) + (a->phase != nullptr) +
+                     (a->k_index != nullptr) + (a->spatial_phase != nullptr);
+  if (tables != 0 && tables != 5)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "forcing: amplitude, omega, phase, k_index and spatial_phase must be given "
+                "together (all NULL = unforced)");
+  if (tables == 5 && (a->nparams < 1 || a->n_k < 1))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "forcing: nparams = %d, n_k = %d (>= 1)", a->nparams,
+                a->n_k);
+  rc = check_dataset_args(a, p);
+  if (rc) return rc;
+  if (a->sample_index == nullptr && a->batch > a->num_rows)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "batch = %d > num_rows = %d without a sample_index", a->batch, a->num_rows);
+  if (a->workspace == nullptr || a->workspace_bytes < ws)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "workspace of %zu bytes given, %s = %zu",
+                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes,
+                "ddd_train_rollout_workspace_bytes", ws);
+  p.weights = a->weights;
+  p.nullspace = projects(p) ? a->nullspace : nullptr;
+  p.bias = projects(p) ? a->bias : nullptr;
+  p.y = a->y0;
+  p.rows = a->num_rows;
+  p.sample_index = a->sample_index;
+  p.ws = static_cast<float*>(a->workspace);
+  p.want_grad = a->grad != nullptr ? 1 : 0;
+  p.grad = a->grad;
+  p.head_means = a->step_means;
+  q.save_every = a->save_every;
+  q.n_saved = a->num_steps / a->save_every;
+  q.dt = (float)a->dt;
+  q.dt64 = a->dt;
+  q.targets = a->targets;
+  q.step_weights = a->step_weights;
+  q.t0 = a->t0;
+  // KdV and KS: finalize_time_derivative is the identity, the tables are ignored
+  q.forced = tables == 5 && is_forced_family(cfg->equation) ? 1 : 0;
+  if (q.forced) {
+    q.P = a->nparams;
+    q.n_k = a->n_k;
+    q.amplitude = a->amplitude;
+    q.omega = a->omega;
+    q.phase = a->phase;
+    q.k_index = a->k_index;
+    q.spatial_phase = a->spatial_phase;
+  }
+  q.trajectory = a->trajectory;
+  DDD_HIP(ddd::train::launch_rollout_loss_grad(q, blocks, lds, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }
 

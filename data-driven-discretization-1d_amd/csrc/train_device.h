@@ -1,6 +1,7 @@
-// Device code shared by the three kernels that differentiate one learned-stencil model
-// evaluation: loss_grad_kernel (train.hip), vjp_kernel (vjp.hip) and
-// unrolled_loss_grad_kernel (train_unrolled.hip).  Activation and equation derivatives, the
+// Device code shared by the kernels that differentiate one learned-stencil model
+// evaluation: loss_grad_kernel (train.hip), vjp_kernel (vjp.hip),
+// unrolled_loss_grad_kernel (train_unrolled.hip) and rollout_loss_grad_kernel
+// (train_rollout.hip).  Activation and equation derivatives, the
 // conv layers on the VALU and on v_mfma_f32_32x32x2_f32, the loss terms of one (point,
 // head), the LDS plan of a workgroup and its prologue, the forward pass of one sample
 // (forward_sample) and its backward pass from a cotangent of the predictions down to the

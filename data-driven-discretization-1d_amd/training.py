@@ -13,6 +13,9 @@ decided on the device).  PopulationTrainer / training_population train R replica
 architecture -- R initial seeds, R learning-rate schedules -- in one such call
 (ddd_train_population_run): the replicas are a second grid dimension of the same kernels,
 and ddd_train_run is the population of one.
+RolloutTrainer / fine_tune_on_rollouts train on the error of the model's own forced
+rollout against exact data (ddd_train_rollout_loss_grad, csrc/train_rollout.hip), over
+windows cut by make_rollout_windows.
 Inferer evaluates a trainer or a population over a whole dataset in one call
 (ddd_eval_metrics, csrc/train_metrics.hip) and returns the reference's calculate_metrics
 (training.py:433-491) per replica; training_loop / training_population(metrics=True) log
@@ -271,6 +274,208 @@ class Trainer(object):
     return model_lib.LearnedStencilModel(
         self.model.equation, self.hparams, kernels, biases, self.model.nullspaces,
         self.model.biases)
+
+
+class RolloutWindows(object):
+  """The windows make_rollout_windows cut: tensors with one row per window (on the device
+  where there is one) and the clock they share."""
+
+  def __init__(self, y0, targets, t0, forcing, dt, num_steps, save_every, sample, start):
+    self.y0 = y0                  # [W, N] float32
+    self.targets = targets        # [W, num_steps // save_every, N] float32
+    self.t0 = t0                  # [W] float64
+    self.forcing = forcing        # forcing_kernel_tables' keys, one row per window, or None
+    self.dt = dt                  # the step of the midpoint rule
+    self.num_steps = num_steps
+    self.save_every = save_every
+    self.sample = sample          # [W] host: the sample of y_exact a window is cut from
+    self.start = start            # [W] host: the index into `times` of its start
+
+  @property
+  def num_windows(self) -> int:
+    return int(self.y0.shape[0])
+
+  @property
+  def num_saved(self) -> int:
+    return self.num_steps // self.save_every
+
+
+def make_rollout_windows(y_exact, times, hparams, num_steps: int, save_every: int,
+                         stride: int = 1, first_seed: int = 0, device=None) -> RolloutWindows:
+  """Training windows of rollout error from exact data: y_exact [sample, time, x_fine] at
+  the uniform `times` is coarse-grained with the equation's own resample method
+  (Grid.resample: block means for conservative equations, subsampling otherwise, as
+  evaluation.RolloutReference and load_initial_conditions do) and cut into windows
+  (sample, start) every `stride` saved times: y0 = the coarse state at times[start], targets
+  the num_steps // save_every saved states after it, t0 = times[start].  The model takes
+  save_every midpoint steps of dt = (times[1] - times[0]) / save_every between two saved
+  times.  Sample i is forced with random_seed = first_seed + i, as run_integrate_batch
+  forces it.  device: 'cuda' where there is one, else 'cpu'."""
+  import torch
+  if device is None:
+    device = 'cuda' if torch.cuda.is_available() else 'cpu'
+  y_exact = np.asarray(y_exact)
+  times = np.asarray(times, np.float64)
+  num_steps, save_every, stride = int(num_steps), int(save_every), int(stride)
+  if y_exact.ndim != 3 or times.ndim != 1 or y_exact.shape[1] != times.shape[0]:
+    raise ValueError('expected y_exact [sample, time, x_fine] and times [time]')
+  if save_every < 1 or num_steps < 1 or num_steps % save_every or stride < 1:
+    raise ValueError('save_every = {} must be >= 1 and divide num_steps = {}; stride = {} '
+                     '(>= 1)'.format(save_every, num_steps, stride))
+  if times.shape[0] < 2:
+    raise ValueError('no window fits: {} saved times'.format(times.shape[0]))
+  steps = np.diff(times)
+  if not (steps[0] > 0) or not np.allclose(steps, steps[0], rtol=1e-9, atol=0.0):
+    raise ValueError('times must be uniform and increasing')
+  _, coarse = equations_lib.from_hparams(hparams, random_seed=first_seed)
+  dt = float(steps[0]) / save_every
+  if dt > coarse.time_step * (1 + 1e-9):
+    raise ValueError('dt = {:g} between model steps exceeds equation.time_step = {:g}: '
+                     'raise save_every'.format(dt, coarse.time_step))
+  grid = coarse.grid
+  if y_exact.shape[2] != grid.reference_num_points:
+    raise ValueError('y_exact has {} points, the reference grid {}'.format(
+        y_exact.shape[2], grid.reference_num_points))
+  num_saved = num_steps // save_every
+  starts = np.arange(0, times.shape[0] - num_saved, stride)
+  if starts.size == 0:
+    raise ValueError('no window fits: {} saved times, {} needed'.format(times.shape[0],
+                                                                        num_saved + 1))
+  low = grid.resample(y_exact.astype(np.float64), axis=-1)   # [sample, time, N]
+  samples = y_exact.shape[0]
+  sample = np.repeat(np.arange(samples), starts.size)
+  start = np.tile(starts, samples)
+  y0 = low[sample, start].astype(np.float32)
+  targets = low[sample[:, None], start[:, None] + 1 + np.arange(num_saved)[None, :]].astype(
+      np.float32)
+  forcing = None
+  if coarse.has_time_dependent_forcing:
+    eqs = [equations_lib.from_hparams(hparams, random_seed=first_seed + i)[1]
+           for i in range(samples)]
+    tables = model_lib.forcing_kernel_tables(model_lib.forcing_from_equations(eqs), grid)
+    forcing = {name: torch.as_tensor(np.ascontiguousarray(tables[name][sample]), device=device)
+               for name in ('amplitude', 'omega', 'phase', 'k_index')}
+    forcing['spatial_phase'] = torch.as_tensor(
+        np.ascontiguousarray(tables['spatial_phase']), device=device)
+  return RolloutWindows(
+      torch.as_tensor(np.ascontiguousarray(y0), device=device),
+      torch.as_tensor(np.ascontiguousarray(targets), device=device),
+      torch.as_tensor(np.ascontiguousarray(times[start]), device=device), forcing, dt,
+      num_steps, save_every, sample, start)
+
+
+class RolloutTrainer(object):
+  """Training on rollout error (ddd_train_rollout_loss_grad, csrc/train_rollout.hip): the
+  flat weight vector, null spaces and Adam(beta2 = 0.99) of Trainer; the loss is
+  sum_j step_weights[j] step_means[j] over the saved steps of RolloutWindows, its gradient
+  one launch.  clip_norm: the gradient is rescaled to that global norm where it exceeds
+  it, on the device."""
+
+  def __init__(self, model: model_lib.LearnedStencilModel, hparams=None, clip_norm=None):
+    hparams = hparams or model.hparams
+    single = copy.copy(hparams)   # (the horizon is the windows', not num_time_steps)
+    single.num_time_steps = 0
+    check_supported(single)
+    base = Trainer(model, hparams)
+    self._base = base
+    self.torch = base.torch
+    self.model, self.hparams, self.cfg = model, hparams, base.cfg
+    self.weights, self.optimizer = base.weights, base.optimizer
+    self.nullspace, self.bias = base.nullspace, base.bias
+    self.clip_norm = None if clip_norm is None else float(clip_norm)
+    self.step_count = 0
+    self.skipped_steps = 0
+    self._workspace = None
+
+  def loss_and_grad(self, windows: RolloutWindows, sample_index=None, step_weights=None,
+                    want_grad=True, want_trajectory=False):
+    """(step_means [num_saved] device, grad or None, trajectory or None) on the windows
+    `sample_index` (int32 device tensor; None: all).  step_weights: [num_saved] host or
+    device values c_j, 1 / num_saved each by default."""
+    torch = self.torch
+    saved = windows.num_saved
+    if step_weights is None:
+      step_weights = torch.full((saved,), 1.0 / saved, dtype=torch.float32,
+                                device=self.weights.device)
+    else:
+      step_weights = torch.as_tensor(step_weights, dtype=torch.float32).to(
+          self.weights.device).contiguous()
+    batch = windows.num_windows if sample_index is None else int(sample_index.shape[0])
+    need = _lib.load_library().ddd_train_rollout_workspace_bytes(
+        self.cfg, batch, windows.num_steps)
+    if self._workspace is None or self._workspace.numel() < need:
+      self._workspace = torch.empty(max(need, 1), dtype=torch.uint8,
+                                    device=self.weights.device)
+    return _lib.train_rollout_loss_grad(
+        self.cfg, self.weights.detach(), windows.y0, windows.targets, step_weights,
+        windows.num_steps, windows.save_every, windows.dt, t0=windows.t0,
+        forcing=windows.forcing, nullspace=self.nullspace, bias=self.bias,
+        sample_index=sample_index, want_grad=want_grad, want_trajectory=want_trajectory,
+        workspace=self._workspace)
+
+  def step(self, windows: RolloutWindows, sample_index, lr: float, step_weights=None):
+    """One optimiser step at learning rate lr on the windows `sample_index`; returns
+    step_means.  A gradient that is not finite everywhere leaves the weights and Adam's
+    state as they are and is counted in skipped_steps."""
+    torch = self.torch
+    means, grad, _ = self.loss_and_grad(windows, sample_index, step_weights)
+    norm = torch.linalg.vector_norm(grad)
+    if not bool(torch.isfinite(norm)):   # (the one host read of a step)
+      self.skipped_steps += 1
+      return means
+    if self.clip_norm is not None:
+      grad = grad * torch.clamp(self.clip_norm / (norm + 1e-12), max=1.0)
+    for group in self.optimizer.param_groups:
+      group['lr'] = float(lr)
+    self.weights.grad = grad
+    self.optimizer.step()
+    self.step_count += 1
+    return means
+
+  def export(self) -> model_lib.LearnedStencilModel:
+    """The current weights as a LearnedStencilModel (same equation / hparams)."""
+    return self._base.export()
+
+
+def fine_tune_on_rollouts(model: model_lib.LearnedStencilModel, y_exact, times, hparams,
+                          checkpoint_dir: str, horizons, save_every: int, batch: int,
+                          learning_rate: float, seed: int = 0, stride: int = 1,
+                          first_seed: int = 0, clip_norm=None) -> List[Dict[str, float]]:
+  """A curriculum of growing horizons over one RolloutTrainer: for every (opt_steps,
+  num_steps) of `horizons`, opt_steps optimiser steps on seeded minibatches of `batch`
+  windows of num_steps model steps (make_rollout_windows of y_exact / times).  Writes
+  hparams.json + model.npz to checkpoint_dir.  Returns one row at the start of every
+  horizon, at every hparams.eval_interval-th step and at the end of every horizon:
+  'step' (over all horizons), 'num_steps', 'loss' and 'step_means' over ALL windows of
+  that horizon (forward only, uniform step weights), and 'skipped_steps' so far."""
+  hparams = copy.deepcopy(hparams)
+  trainer = RolloutTrainer(model, hparams, clip_norm=clip_norm)
+  torch = trainer.torch
+  os.makedirs(checkpoint_dir, exist_ok=True)
+  hparams_lib.save_hparams(hparams, checkpoint_dir)
+  rs = np.random.RandomState(seed)
+  rows, step = [], 0
+
+  def evaluate(windows):
+    means, _, _ = trainer.loss_and_grad(windows, want_grad=False)
+    means = means.double().cpu().numpy()
+    rows.append({'step': step, 'num_steps': windows.num_steps, 'loss': float(means.mean()),
+                 'step_means': means.tolist(), 'skipped_steps': trainer.skipped_steps})
+
+  for opt_steps, num_steps in horizons:
+    windows = make_rollout_windows(y_exact, times, hparams, num_steps, save_every,
+                                   stride=stride, first_seed=first_seed)
+    count = min(int(batch), windows.num_windows)
+    evaluate(windows)
+    for k in range(int(opt_steps)):
+      index = torch.as_tensor(rs.choice(windows.num_windows, size=count, replace=False)
+                              .astype(np.int32), device=trainer.weights.device)
+      trainer.step(windows, index, learning_rate)
+      step += 1
+      if step % hparams.eval_interval == 0 or k == int(opt_steps) - 1:
+        evaluate(windows)
+  trainer.export().save(checkpoint_dir)
+  return rows
 
 
 class PopulationTrainer(object):

@@ -547,6 +547,78 @@ DDD_API size_t ddd_train_unrolled_workspace_bytes(const ddd_config* cfg, int bat
 DDD_API int ddd_train_unrolled_loss_grad(const ddd_config* cfg,
                                          const ddd_train_unrolled_args* args, void* stream);
 
+/* ---- training on rollout error ----------------------------------------------
+ * The loss is the error of a rollout itself: from each window start y0 the model's
+ * own midpoint-rule trajectory over T = num_steps steps of size dt, FORCED as the
+ * equation is forced, compared at every save_every-th step with given targets
+ * (e.g. the coarse-grained exact solution), and the gradient of that loss with
+ * respect to every conv kernel and bias, in one launch plus the fixed-order slab
+ * sum.  Per window (row):
+ *   y_{s+1} = y_s + dt f(t_s + dt/2, y_s + (dt/2) f(t_s, y_s)),
+ *   f(t, y) = the time derivative of ddd_train_loss_grad's last head (equation of
+ *             motion) + forcing_row(x, t), the forcing of ddd_set_forcing in the
+ *             same float32 order, added after the flux difference; t is formed in
+ *             float64 as t0[row] + s dt (+ dt/2) and rounded to float32.  Ignored
+ *             by KdV and KS, as ddd_set_forcing documents.
+ *   step_means[j] = mean over (sample, x) of (y_{(j+1) save_every} - targets[j])^2
+ *   loss = sum_j step_weights[j] step_means[j]
+ * The forcing depends on neither the state nor the weights: the adjoint is that of
+ * ddd_train_unrolled_loss_grad with cotangents entering at saved steps only, and
+ * an unforced call with save_every = 1 repeats that entry point's integrated
+ * heads bit for bit.  All 2 T stage states of a window are kept in the workspace
+ * (2 T N floats per workgroup, at most 512 workgroups) next to the saved-step
+ * cotangents; the loss constants are a DEVICE array, so T is not tied to
+ * DDD_MAX_TIME_STEPS.  Supports exactly the configurations ddd_train_loss_grad
+ * supports, named "ddd_train_rollout_loss_grad" in the messages.
+ * DDD_ERR_INVALID_ARGUMENT: num_steps outside [1, DDD_MAX_ROLLOUT_STEPS],
+ * save_every < 1 or not a divisor of num_steps, dt <= 0, a struct_size mismatch,
+ * NULL y0 / targets / step_weights / step_means, forcing pointers partly given. */
+#define DDD_MAX_ROLLOUT_STEPS 256
+
+typedef struct ddd_train_rollout_args {
+  int32_t struct_size;   /* = sizeof(ddd_train_rollout_args), checked */
+  int32_t batch;         /* windows in the minibatch */
+  int32_t num_rows;      /* S: rows of y0 / targets / t0 / the forcing tables */
+  int32_t num_steps;     /* T */
+  int32_t save_every;    /* a divisor of T; T / save_every saved steps */
+  const float* weights;  /* as ddd_train_args */
+  const float* nullspace; /* as ddd_train_args */
+  const float* bias;     /* as ddd_train_args */
+  const float* y0;       /* device [S][N] window starts */
+  const int32_t* sample_index; /* as ddd_train_args: an index outside [0, S) makes
+                                  step_means and that sample's trajectory rows NaN */
+  const float* targets;  /* device [S][T / save_every][N] */
+  const float* step_weights; /* device [T / save_every]: c_j */
+  double dt;             /* step of the midpoint rule */
+  const double* t0;      /* device [S]: start time per row, NULL = 0 */
+  /* forcing, one row per row of y0: the tables of ddd_set_forcing as DEVICE arrays;
+   * amplitude NULL (then all five NULL) = unforced.  A k_index outside [0, n_k)
+   * reads nothing and makes that row's trajectory NaN. */
+  int32_t nparams, n_k;
+  const float* amplitude;     /* [S][nparams] */
+  const float* omega;         /* [S][nparams] */
+  const float* phase;         /* [S][nparams] */
+  const int32_t* k_index;     /* [S][nparams] */
+  const float* spatial_phase; /* [n_k][N] */
+  float* step_means;     /* out [T / save_every] */
+  float* grad;           /* out, layout of `weights`; NULL = forward and loss only */
+  float* trajectory;     /* out [batch][T / save_every][N] or NULL */
+  void* workspace;       /* ddd_train_rollout_workspace_bytes(cfg, batch, T) bytes */
+  size_t workspace_bytes;
+} ddd_train_rollout_args;
+
+/* Bytes of the caller-allocated workspace of ddd_train_rollout_loss_grad for any
+ * save_every (partial gradient slabs, per-workgroup scratch, stage states and
+ * saved-step cotangents); 0 on an unsupported configuration or num_steps out of range. */
+DDD_API size_t ddd_train_rollout_workspace_bytes(const ddd_config* cfg, int batch,
+                                                 int num_steps);
+/* step_means and, with grad non-NULL, the gradient of sum_j step_weights[j]
+ * step_means[j] with respect to every conv kernel and bias.  Deterministic,
+ * sample_index, grad = NULL and trajectory = NULL as ddd_train_unrolled_loss_grad
+ * (there: predictions). */
+DDD_API int ddd_train_rollout_loss_grad(const ddd_config* cfg,
+                                        const ddd_train_rollout_args* args, void* stream);
+
 /* ---- the optimiser loop on the device --------------------------------------
  * Replaces: num_steps iterations of training.training_loop (training.py:570-636)
  * between two evaluations: per step the loss and gradient of
