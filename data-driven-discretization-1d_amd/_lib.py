@@ -223,6 +223,50 @@ class DDDTrainPopulationArgs(ctypes.Structure):
   ]
 
 
+class DDDTrainRolloutRunArgs(ctypes.Structure):
+  """struct ddd_train_rollout_run_args."""
+  _fields_ = [
+      ('struct_size', ctypes.c_int32),
+      ('batch', ctypes.c_int32),
+      ('num_rows', ctypes.c_int32),
+      ('num_steps', ctypes.c_int32),
+      ('save_every', ctypes.c_int32),
+      ('num_opt_steps', ctypes.c_int32),
+      ('replicas', ctypes.c_int32),
+      ('index_per_replica', ctypes.c_int32),
+      ('forward_only', ctypes.c_int32),
+      ('weights', ctypes.c_void_p),
+      ('adam_m', ctypes.c_void_p),
+      ('adam_v', ctypes.c_void_p),
+      ('adam_step', ctypes.c_void_p),
+      ('nullspace', ctypes.c_void_p),
+      ('bias', ctypes.c_void_p),
+      ('y0', ctypes.c_void_p),
+      ('targets', ctypes.c_void_p),
+      ('step_weights', ctypes.c_void_p),
+      ('dt', ctypes.c_double),
+      ('t0', ctypes.c_void_p),
+      ('nparams', ctypes.c_int32),
+      ('n_k', ctypes.c_int32),
+      ('amplitude', ctypes.c_void_p),
+      ('omega', ctypes.c_void_p),
+      ('phase', ctypes.c_void_p),
+      ('k_index', ctypes.c_void_p),
+      ('spatial_phase', ctypes.c_void_p),
+      ('sample_index', ctypes.c_void_p),
+      ('learning_rate', ctypes.POINTER(ctypes.c_double)),
+      ('beta1', ctypes.c_double),
+      ('beta2', ctypes.c_double),
+      ('epsilon', ctypes.c_double),
+      ('clip_norm', ctypes.c_double),
+      ('step_means_log', ctypes.c_void_p),
+      ('grad_norm_log', ctypes.c_void_p),
+      ('last_grad', ctypes.c_void_p),
+      ('workspace', ctypes.c_void_p),
+      ('workspace_bytes', ctypes.c_size_t),
+  ]
+
+
 class DDDEvalMetricsArgs(ctypes.Structure):
   """struct ddd_eval_metrics_args."""
   _fields_ = [
@@ -426,6 +470,11 @@ SIGNATURES = {
                                               ctypes.c_int, ctypes.c_int]),
     'ddd_train_population_run': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
                                                 ctypes.POINTER(DDDTrainPopulationArgs), _V]),
+    'ddd_train_rollout_run_workspace_bytes': (ctypes.c_size_t,
+                                              [ctypes.POINTER(DDDConfig), ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int]),
+    'ddd_train_rollout_run': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
+                                             ctypes.POINTER(DDDTrainRolloutRunArgs), _V]),
     'ddd_eval_metrics_workspace_bytes': (ctypes.c_size_t,
                                          [ctypes.POINTER(DDDConfig), ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int]),
@@ -981,6 +1030,124 @@ def train_population_run(cfg, weights, adam_m, adam_v, y, labels, baseline, samp
       replicas, rates, cfg, weights, adam_m, adam_v, y, labels, baseline, sample_index,
       error_floor, coef_abs, coef_rel, first_step, betas, epsilon, steps, time_step, error_max,
       error_scale, nullspace, bias, want_last_grad, workspace)
+
+
+def train_rollout_run(cfg, weights, adam_m, adam_v, adam_step, y0, targets, step_weights,
+                      num_steps, save_every, dt, sample_index, learning_rates,
+                      betas=(0.9, 0.999), epsilon=1e-8, clip_norm=0.0, t0=None, forcing=None,
+                      nullspace=None, bias=None, forward_only=False, want_last_grad=False,
+                      workspace=None):
+  """ddd_train_rollout_run: K optimiser steps on rollout error for R replicas, enqueued on
+  the current stream; returns (step_means_log [K, R, T / save_every], grad_norm_log [K, R],
+  last_grad [R, n_weights] or None) as device tensors, without waiting for the device.
+
+  weights / adam_m / adam_v are [R, n_weights] float32 (rows in the ddd_model_create layout;
+  a tensor with more rows is taken as its first R) and adam_step int32 [R], all updated in
+  place; learning_rates host floats [R][K]; sample_index an int32 device tensor [K, batch]
+  (one minibatch order for all replicas) or [K, R, batch].  A step whose gradient norm is not
+  finite is skipped for that replica: its row of grad_norm_log is not finite then.  The
+  windows (y0, targets, step_weights, dt, t0, forcing) as train_rollout_loss_grad.
+
+  forward_only: one loss pass per replica over the rows `sample_index` ([1, batch] or
+  [1, R, batch]; None: all rows); adam_m / adam_v / adam_step / learning_rates may be None
+  (R is then weights' rows) and grad_norm_log is returned as None."""
+  lib = load_library()
+  torch = require_gpu()
+  steps, every = int(num_steps), int(save_every)
+  if every < 1 or steps < 1 or steps % every:
+    raise ValueError('save_every = {} must be >= 1 and divide num_steps = {}'.format(
+        every, steps))
+  saved = steps // every
+  if forward_only:
+    replicas, opt_steps = int(weights.shape[0]), 1
+    rates = None
+  else:
+    rates = [[float(rate) for rate in row] for row in learning_rates]
+    replicas = len(rates)
+    if not rates or any(len(row) != len(rates[0]) for row in rates):
+      raise ValueError('learning_rates must be [R][K]')
+    opt_steps = len(rates[0])
+  if y0.dim() != 2 or y0.shape[1] != cfg.num_points:
+    raise ValueError('expected y0 [S, N]')
+  rows, n = int(y0.shape[0]), int(y0.shape[1])
+  if sample_index is None:
+    if not forward_only:
+      raise ValueError('sample_index is required')
+    batch = rows
+  else:
+    if (not isinstance(sample_index, torch.Tensor) or sample_index.dtype != torch.int32 or
+        not sample_index.is_cuda or not sample_index.is_contiguous() or
+        sample_index.dim() not in (2, 3) or int(sample_index.shape[0]) != opt_steps or
+        (sample_index.dim() == 3 and int(sample_index.shape[1]) != replicas)):
+      raise ValueError('sample_index must be a contiguous int32 device tensor [K, batch] or '
+                       '[K, R, batch]')
+    batch = int(sample_index.shape[-1])
+  n_weights = vjp_num_weights(cfg)
+  state = [('weights', weights)]
+  if not forward_only:
+    state += [('adam_m', adam_m), ('adam_v', adam_v)]
+    _check_device('adam_step', adam_step, torch.int32, (replicas,))
+  for name, tensor in state:
+    given = int(tensor.shape[0]) if isinstance(tensor, torch.Tensor) and tensor.dim() == 2 else 0
+    if given < replicas:
+      raise ValueError('{} must be [R, n_weights] with R = {} rows'.format(name, replicas))
+    _check_f32_device(name, tensor, (given, n_weights))
+  _check_f32_device('y0', y0, (rows, n))
+  _check_f32_device('targets', targets, (rows, saved, n))
+  _check_f32_device('step_weights', step_weights, (saved,))
+  for name, tensor in (('nullspace', nullspace), ('bias', bias)):
+    if tensor is not None:
+      _check_f32_device(name, tensor, tuple(tensor.shape))
+  if t0 is not None:
+    _check_device('t0', t0, torch.float64, (rows,))
+  args = DDDTrainRolloutRunArgs()
+  if forcing is not None:
+    nparams = int(forcing['amplitude'].shape[1])
+    n_k = int(forcing['spatial_phase'].shape[0])
+    for name in ('amplitude', 'omega', 'phase'):
+      _check_f32_device(name, forcing[name], (rows, nparams))
+    _check_device('k_index', forcing['k_index'], torch.int32, (rows, nparams))
+    _check_f32_device('spatial_phase', forcing['spatial_phase'], (n_k, n))
+    args.nparams, args.n_k = nparams, n_k
+    for name in ('amplitude', 'omega', 'phase', 'k_index', 'spatial_phase'):
+      setattr(args, name, forcing[name].data_ptr())
+  ws_bytes = lib.ddd_train_rollout_run_workspace_bytes(ctypes.byref(cfg), batch, steps, replicas)
+  if ws_bytes == 0:
+    check(-1)
+  if workspace is None or workspace.numel() < ws_bytes:
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y0.device)
+  log = torch.empty((opt_steps, replicas, saved), dtype=torch.float32, device=y0.device)
+  norms = (None if forward_only else
+           torch.empty((opt_steps, replicas), dtype=torch.float32, device=y0.device))
+  last_grad = (torch.empty((replicas, n_weights), dtype=torch.float32, device=y0.device)
+               if want_last_grad and not forward_only else None)
+  args.struct_size = ctypes.sizeof(args)
+  args.batch = batch
+  args.num_rows = rows
+  args.num_steps = steps
+  args.save_every = every
+  args.num_opt_steps = opt_steps
+  args.replicas = replicas
+  args.index_per_replica = 1 if sample_index is not None and sample_index.dim() == 3 else 0
+  args.forward_only = 1 if forward_only else 0
+  for name, tensor in (('weights', weights), ('adam_m', adam_m), ('adam_v', adam_v),
+                       ('adam_step', adam_step), ('nullspace', nullspace), ('bias', bias),
+                       ('y0', y0), ('targets', targets), ('step_weights', step_weights),
+                       ('t0', t0), ('sample_index', sample_index), ('step_means_log', log),
+                       ('grad_norm_log', norms), ('last_grad', last_grad)):
+    setattr(args, name, None if tensor is None else tensor.data_ptr())
+  args.dt = float(dt)
+  if rates is not None:
+    flat = [rate for row in rates for rate in row]
+    rate_array = (ctypes.c_double * len(flat))(*flat)
+    args.learning_rate = ctypes.cast(rate_array, ctypes.POINTER(ctypes.c_double))
+  args.beta1, args.beta2 = float(betas[0]), float(betas[1])
+  args.epsilon = float(epsilon)
+  args.clip_norm = float(clip_norm or 0.0)
+  args.workspace = workspace.data_ptr()
+  args.workspace_bytes = workspace.numel()
+  check(lib.ddd_train_rollout_run(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
+  return log, norms, last_grad
 
 
 def eval_metrics(cfg, weights, y, labels, baseline, error_floor, coef_abs, coef_rel,

@@ -40,6 +40,7 @@
 #include "train_metrics.h"
 #include "train_population.h"
 #include "train_rollout.h"
+#include "train_rollout_population.h"
 #include "train_unrolled.h"
 #include "rhs_weno.h"   // (host side only: weno::supports; the kernels are weno_unit.hip)
 
@@ -1515,15 +1516,15 @@ int train_unrolled_params(const ddd_config* cfg, int batch, int num_time_steps,
 
 static_assert(ddd::train::kMaxRolloutSteps == DDD_MAX_ROLLOUT_STEPS, "train_rollout.h / ddd1d.h");
 
-// train_params for ddd_train_rollout_loss_grad (train_rollout.h) under that name: the
+// train_params for ddd_train_rollout_loss_grad (train_rollout.h) under that name (`who`:
+// ddd_train_rollout_run passes its own): the
 // same checks and messages, then num_steps.  A slab is laid out for save_every = 1 (the
 // workspace function does not know it): num_steps sums behind the gradient, then the
 // pre-activations, the 2 T stage states and up to T saved-step cotangents.  The LDS plan
 // and its 160 KiB check are train_unrolled_params'.
 int train_rollout_params(const ddd_config* cfg, int batch, int num_steps,
                          ddd::train::RolloutParams* rp, int* blocks, size_t* ws_bytes,
-                         size_t* lds_bytes) {
-  const char* who = "ddd_train_rollout_loss_grad";
+                         size_t* lds_bytes, const char* who = "ddd_train_rollout_loss_grad") {
   std::memset(rp, 0, sizeof(*rp));
   ddd::train::TrainParams& p = rp->t;
   int rc = train_params(cfg, batch, &p, blocks, ws_bytes, lds_bytes, who);
@@ -1776,6 +1777,83 @@ int train_args(const Args* a, ddd::train::TrainParams& p, size_t ws, const char*
   p.want_grad = a->grad != nullptr ? 1 : 0;
   p.grad = a->grad;
   p.head_means = a->head_means;
+  return DDD_OK;
+}
+
+// What ddd_train_rollout_loss_grad and ddd_train_rollout_run check and copy alike of the
+// windows, for Args = ddd_train_rollout_args / ddd_train_rollout_run_args (equally named
+// fields): save_every, dt, the window tensors, the forcing tables, the projection tables,
+// num_rows and the workspace of at least ws bytes (named ws_bytes_fn in the message), then
+// all of them into q, whose configuration train_rollout_params has filled.
+template <typename Args>
+int take_rollout_windows(const ddd_config* cfg, const Args* a, ddd::train::RolloutParams& q,
+                         size_t ws, const char* ws_bytes_fn) {
+  ddd::train::TrainParams& p = q.t;
+  if (a->save_every < 1 || a->num_steps % a->save_every != 0)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "save_every = %d must be >= 1 and divide num_steps = %d",
+                a->save_every, a->num_steps);
+  if (!(a->dt > 0.0) || !std::isfinite(a->dt))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "dt = %g must be positive and finite", a->dt);
+  if (!a->y0 || !a->targets || !a->step_weights)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "y0, targets and step_weights must not be NULL");
+  const int tables = (a->amplitude != nullptr) + (a->omega != nullptr) + (a->phase != nullptr) +
+                     (a->k_index != nullptr) + (a->spatial_phase != nullptr);
+  if (tables != 0 && tables != 5)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "forcing: amplitude, omega, phase, k_index and spatial_phase must be given "
+                "together (all NULL = unforced)");
+  if (tables == 5 && (a->nparams < 1 || a->n_k < 1))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "forcing: nparams = %d, n_k = %d (>= 1)", a->nparams,
+                a->n_k);
+  int rc = check_dataset_args(a, p);
+  if (rc) return rc;
+  if (a->sample_index == nullptr && a->batch > a->num_rows)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "batch = %d > num_rows = %d without a sample_index", a->batch, a->num_rows);
+  if (a->workspace == nullptr || a->workspace_bytes < ws)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "workspace of %zu bytes given, %s = %zu",
+                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws_bytes_fn, ws);
+  p.nullspace = projects(p) ? a->nullspace : nullptr;
+  p.bias = projects(p) ? a->bias : nullptr;
+  p.y = a->y0;
+  p.rows = a->num_rows;
+  p.ws = static_cast<float*>(a->workspace);
+  q.save_every = a->save_every;
+  q.n_saved = a->num_steps / a->save_every;
+  q.dt = (float)a->dt;
+  q.dt64 = a->dt;
+  q.targets = a->targets;
+  q.step_weights = a->step_weights;
+  q.t0 = a->t0;
+  // KdV and KS: finalize_time_derivative is the identity, the tables are ignored
+  q.forced = tables == 5 && is_forced_family(cfg->equation) ? 1 : 0;
+  if (q.forced) {
+    q.P = a->nparams;
+    q.n_k = a->n_k;
+    q.amplitude = a->amplitude;
+    q.omega = a->omega;
+    q.phase = a->phase;
+    q.k_index = a->k_index;
+    q.spatial_phase = a->spatial_phase;
+  }
+  return DDD_OK;
+}
+
+// train_rollout_params under the name "ddd_train_rollout_run", then the replica count.
+// *slab_bytes: the slabs of ONE replica (ddd_train_rollout_workspace_bytes); *ws_bytes: the
+// whole workspace, R times the slabs and the tail of train_rollout_population.h.
+int train_rollout_run_params(const ddd_config* cfg, int batch, int num_steps, int replicas,
+                             ddd::train::RolloutRunParams* rr, size_t* slab_bytes,
+                             size_t* ws_bytes) {
+  std::memset(rr, 0, sizeof(*rr));
+  int rc = train_rollout_params(cfg, batch, num_steps, &rr->q, &rr->blocks, slab_bytes,
+                                &rr->lds_bytes, "ddd_train_rollout_run");
+  if (rc) return rc;
+  if (replicas < 1 || replicas > DDD_MAX_REPLICAS)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "replicas = %d out of range [1, %d]", replicas,
+                DDD_MAX_REPLICAS);
+  *ws_bytes = (size_t)replicas * *slab_bytes +
+              ddd::train::rollout_run_tail_bytes(rr->q.t.n_weights, num_steps, replicas);
   return DDD_OK;
 }
 
@@ -3196,62 +3274,100 @@ int ddd_train_rollout_loss_grad(const ddd_config* cfg, const ddd_train_rollout_a
   size_t ws = 0, lds = 0;
   int rc = train_rollout_params(cfg, a->batch, a->num_steps, &q, &blocks, &ws, &lds);
   if (rc) return rc;
-  if (a->save_every < 1 || a->num_steps % a->save_every != 0)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "save_every = %d must be >= 1 and divide num_steps = %d",
-                a->save_every, a->num_steps);
-  if (!(a->dt > 0.0) || !std::isfinite(a->dt))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "dt = %g must be positive and finite", a->dt);
-  if (!a->weights || !a->y0 || !a->targets || !a->step_weights || !a->step_means)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "weights, y0, targets, step_weights and step_means must not be NULL");
-  const int tables = (a->amplitude != nullptr) + (a->omega != nullptr) + (a->phase != nullptr) +
-                     (a->k_index != nullptr) + (a->spatial_phase != nullptr);
-  if (tables != 0 && tables != 5)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "forcing: amplitude, omega, phase, k_index and spatial_phase must be given "
-                "together (all NULL = unforced)");
-  if (tables == 5 && (a->nparams < 1 || a->n_k < 1))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "forcing: nparams = %d, n_k = %d (>= 1)", a->nparams,
-                a->n_k);
-  rc = check_dataset_args(a, p);
+  if (!a->weights || !a->step_means)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "weights and step_means must not be NULL");
+  rc = take_rollout_windows(cfg, a, q, ws, "ddd_train_rollout_workspace_bytes");
   if (rc) return rc;
-  if (a->sample_index == nullptr && a->batch > a->num_rows)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "batch = %d > num_rows = %d without a sample_index", a->batch, a->num_rows);
-  if (a->workspace == nullptr || a->workspace_bytes < ws)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "workspace of %zu bytes given, %s = %zu",
-                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes,
-                "ddd_train_rollout_workspace_bytes", ws);
   p.weights = a->weights;
-  p.nullspace = projects(p) ? a->nullspace : nullptr;
-  p.bias = projects(p) ? a->bias : nullptr;
-  p.y = a->y0;
-  p.rows = a->num_rows;
   p.sample_index = a->sample_index;
-  p.ws = static_cast<float*>(a->workspace);
   p.want_grad = a->grad != nullptr ? 1 : 0;
   p.grad = a->grad;
   p.head_means = a->step_means;
-  q.save_every = a->save_every;
-  q.n_saved = a->num_steps / a->save_every;
-  q.dt = (float)a->dt;
-  q.dt64 = a->dt;
-  q.targets = a->targets;
-  q.step_weights = a->step_weights;
-  q.t0 = a->t0;
-  // KdV and KS: finalize_time_derivative is the identity, the tables are ignored
-  q.forced = tables == 5 && is_forced_family(cfg->equation) ? 1 : 0;
-  if (q.forced) {
-    q.P = a->nparams;
-    q.n_k = a->n_k;
-    q.amplitude = a->amplitude;
-    q.omega = a->omega;
-    q.phase = a->phase;
-    q.k_index = a->k_index;
-    q.spatial_phase = a->spatial_phase;
-  }
   q.trajectory = a->trajectory;
   DDD_HIP(ddd::train::launch_rollout_loss_grad(q, blocks, lds, static_cast<hipStream_t>(stream)));
+  return DDD_OK;
+}
+
+size_t ddd_train_rollout_run_workspace_bytes(const ddd_config* cfg, int batch, int num_steps,
+                                             int replicas) {
+  ddd::train::RolloutRunParams rr;
+  size_t slabs = 0, ws = 0;
+  if (train_rollout_run_params(cfg, batch, num_steps, replicas, &rr, &slabs, &ws)) return 0;
+  return ws;
+}
+
+int ddd_train_rollout_run(const ddd_config* cfg, const ddd_train_rollout_run_args* a,
+                          void* stream) {
+  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
+  if (a->struct_size != (int32_t)sizeof(ddd_train_rollout_run_args))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_train_rollout_run_args.struct_size = %d, library expects %d (ABI mismatch)",
+                a->struct_size, (int)sizeof(ddd_train_rollout_run_args));
+  ddd::train::RolloutRunParams rr;
+  ddd::train::RolloutParams& q = rr.q;
+  ddd::train::TrainParams& p = q.t;
+  size_t slabs = 0, ws = 0;
+  int rc = train_rollout_run_params(cfg, a->batch, a->num_steps, a->replicas, &rr, &slabs, &ws);
+  if (rc) return rc;
+  const int R = a->replicas, K = a->num_opt_steps;
+  if (a->index_per_replica != 0 && a->index_per_replica != 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "index_per_replica = %d (0 or 1)",
+                a->index_per_replica);
+  if (a->forward_only != 0 && a->forward_only != 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "forward_only = %d (0 or 1)", a->forward_only);
+  if (K < 1 || (a->forward_only && K != 1))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "num_opt_steps = %d (>= 1; 1 with forward_only)", K);
+  if (!a->weights || !a->step_means_log)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "weights and step_means_log must not be NULL");
+  if (!a->forward_only) {
+    if (!a->adam_m || !a->adam_v || !a->adam_step || !a->sample_index || !a->learning_rate ||
+        !a->grad_norm_log)
+      return fail(DDD_ERR_INVALID_ARGUMENT,
+                  "adam_m, adam_v, adam_step, sample_index, learning_rate and grad_norm_log "
+                  "must not be NULL");
+    for (int i = 0; i < R; ++i)
+      for (int k = 0; k < K; ++k) {
+        const double rate = a->learning_rate[(size_t)i * K + k];
+        if (!std::isfinite(rate) || rate < 0.0)
+          return fail(DDD_ERR_INVALID_ARGUMENT,
+                      "learning_rate of replica %d, step %d is %g (finite, >= 0)", i, k, rate);
+      }
+    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0) || !(a->beta2 >= 0.0 && a->beta2 < 1.0))
+      return fail(DDD_ERR_INVALID_ARGUMENT, "beta1 = %g, beta2 = %g outside [0, 1)", a->beta1,
+                  a->beta2);
+    if (!(a->epsilon > 0.0) || !std::isfinite(a->epsilon))
+      return fail(DDD_ERR_INVALID_ARGUMENT, "epsilon = %g (> 0)", a->epsilon);
+    if (!(a->clip_norm >= 0.0) || !std::isfinite(a->clip_norm))
+      return fail(DDD_ERR_INVALID_ARGUMENT, "clip_norm = %g (>= 0, finite)", a->clip_norm);
+  }
+  rc = take_rollout_windows(cfg, a, q, ws, "ddd_train_rollout_run_workspace_bytes");
+  if (rc) return rc;
+  p.weights = a->weights;
+  rr.replicas = R;
+  rr.index_per_replica = a->index_per_replica;
+  rr.forward_only = a->forward_only;
+  rr.num_opt_steps = K;
+  rr.learning_rate = a->learning_rate;
+  rr.beta1 = a->beta1;
+  rr.beta2 = a->beta2;
+  rr.epsilon = a->epsilon;
+  rr.clip_norm = a->clip_norm;
+  rr.sample_index = a->sample_index;
+  rr.weights = a->weights;
+  rr.adam_m = a->adam_m;
+  rr.adam_v = a->adam_v;
+  rr.adam_step = a->adam_step;
+  rr.step_means_log = a->step_means_log;
+  rr.grad_norm_log = a->grad_norm_log;
+  rr.last_grad = a->last_grad;
+  // behind the R replicas' slabs: the gradients, the partial sums, the decision records
+  char* tail = static_cast<char*>(a->workspace) + (size_t)R * slabs;
+  rr.grad_buf = reinterpret_cast<float*>(tail);
+  tail += ((size_t)R * p.n_weights * sizeof(float) + 15) & ~(size_t)15;
+  rr.partials = reinterpret_cast<double*>(tail);
+  rr.decisions = reinterpret_cast<ddd::train::RolloutDecision*>(
+      static_cast<char*>(a->workspace) + ws - (size_t)R * sizeof(ddd::train::RolloutDecision));
+  DDD_HIP(ddd::train::launch_train_rollout_run(rr, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }
 

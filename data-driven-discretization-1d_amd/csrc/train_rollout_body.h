@@ -4,7 +4,9 @@
 // constants read from the device.  The update expressions (u + half_dt k1, y_s + dt k2),
 // the cotangent ((2 (y - target)) c) / (batch N) and the order of the slab additions are
 // that body's, so that an unforced call with save_every = 1 repeats its integrated heads
-// bit for bit.  A workgroup is blockIdx.x of gridDim.x.
+// bit for bit.  A workgroup is blockIdx.x of gridDim.x.  Shared by rollout_loss_grad_kernel
+// (train_rollout.hip) and the replica form of the optimiser loop
+// (train_rollout_population.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +34,9 @@ __device__ __forceinline__ float rollout_forcing(const RolloutParams& q, int row
   return total;
 }
 
+// kReplicas: workgroup (blockIdx.x, blockIdx.y) is workgroup blockIdx.x of replica blockIdx.y
+// (weights_of, train_device.h)
+template <bool kReplicas = false>
 __device__ __forceinline__ void rollout_loss_grad_body(const RolloutParams& q) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const TrainParams& p = q.t;
@@ -39,7 +44,9 @@ __device__ __forceinline__ void rollout_loss_grad_body(const RolloutParams& q) {
   const int T = q.T, E = 2 * T;   // E evaluations: 2 s at y_s, 2 s + 1 at y_mid_s
   const int every = q.save_every, n_saved = q.n_saved;
   const Rows r = carve_rows(p, smem, true);
-  float* slab = p.ws + (size_t)blockIdx.x * p.slab_stride;
+  float* slab = kReplicas
+                    ? p.ws + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * p.slab_stride
+                    : p.ws + (size_t)blockIdx.x * p.slab_stride;
   float* zs = slab + p.n_slab;
   float* st = slab + q.st_off;   // [E][N] stage states
   float* gi = slab + q.gi_off;   // [n_saved][N] loss cotangents of the saved steps
@@ -47,16 +54,20 @@ __device__ __forceinline__ void rollout_loss_grad_body(const RolloutParams& q) {
   const float inv_count = 1.0f / ((float)p.batch * (float)n);
   const float dt = q.dt, half_dt = 0.5f * q.dt;
 
-  stage_workgroup(p, slab, p.n_slab, r.wl);
+  stage_workgroup<kReplicas>(p, slab, p.n_slab, r.wl);
 
   for (int s = blockIdx.x; s < p.batch; s += gridDim.x) {
-    const int row = p.sample_index != nullptr ? p.sample_index[s] : s;
+    const int* index =
+        kReplicas ? p.sample_index + (size_t)blockIdx.y * p.index_stride : p.sample_index;
+    const int row = p.sample_index != nullptr ? index[s] : s;
     const size_t yoff = (size_t)s * n_saved * n;
     if (row < 0 || row >= p.rows) {
       // an index outside [0, rows): no input read, the call's step means and this sample's
       // trajectory rows become NaN
       const float nan = __int_as_float(0x7fc00000);
       if (tid < n_saved) sums[tid] = nan;
+      if (kReplicas)   // ... and, for the update, the replica's gradient (ddd1d.h)
+        for (int i = tid; i < p.n_weights; i += kThreads) slab[i] = nan;
       if (q.trajectory != nullptr)
         for (int i = tid; i < n_saved * n; i += kThreads) q.trajectory[yoff + i] = nan;
       continue;   // (block-uniform)
@@ -82,7 +93,7 @@ __device__ __forceinline__ void rollout_loss_grad_body(const RolloutParams& q) {
       __syncthreads();
       float* cur = r.buf0;
       float* nxt = r.buf1;
-      forward_sample(p, r.wl, zs, r.u, r.gfl, r.pred, cur, nxt);
+      forward_sample<kReplicas>(p, r.wl, zs, r.u, r.gfl, r.pred, cur, nxt);
       // the evaluation's time: float64 on the clock of the window, rounded once
       const double t64 = t_start + (double)step * q.dt64 + (mid ? 0.5 * q.dt64 : 0.0);
       const float t = (float)t64;
@@ -133,8 +144,8 @@ __device__ __forceinline__ void rollout_loss_grad_body(const RolloutParams& q) {
       __syncthreads();
       // g_mid to its own row; g_s to gdy (free once the product has read it); lam_0 is
       // not an output, so the last product skips the state gradient
-      evaluation_vjp<true>(p, r, zs, cur, nxt, slab, true,
-                           mid ? r.gmid : (e > 0 ? r.gdy : nullptr));
+      evaluation_vjp<true, kReplicas>(p, r, zs, cur, nxt, slab, true,
+                                      mid ? r.gmid : (e > 0 ? r.gdy : nullptr));
       if (!mid && e > 0) {
         const bool saved = step % every == 0;   // y_step carries a loss term
         const int j = step / every - 1;

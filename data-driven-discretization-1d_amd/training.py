@@ -15,7 +15,11 @@ architecture -- R initial seeds, R learning-rate schedules -- in one such call
 and ddd_train_run is the population of one.
 RolloutTrainer / fine_tune_on_rollouts train on the error of the model's own forced
 rollout against exact data (ddd_train_rollout_loss_grad, csrc/train_rollout.hip), over
-windows cut by make_rollout_windows.
+windows cut by make_rollout_windows.  RolloutTrainer.run / fine_tune_on_rollouts(fused=True)
+hand a stretch of such steps to the device (ddd_train_rollout_run,
+csrc/train_rollout_population.hip: norm, skip, clip and Adam decided there), and
+RolloutPopulationTrainer / fine_tune_population_on_rollouts do so for R replicas at once;
+PopulationTrainer.rollout_trainer() fine-tunes a trained population where it lies.
 Inferer evaluates a trainer or a population over a whole dataset in one call
 (ddd_eval_metrics, csrc/train_metrics.hip) and returns the reference's calculate_metrics
 (training.py:433-491) per replica; training_loop / training_population(metrics=True) log
@@ -364,12 +368,36 @@ def make_rollout_windows(y_exact, times, hparams, num_steps: int, save_every: in
       num_steps, save_every, sample, start)
 
 
+def _rollout_step_weights(windows: RolloutWindows, step_weights, device):
+  """The loss constants c_j as a float32 device tensor [num_saved]: 1 / num_saved each by
+  default, else the given host or device values."""
+  import torch
+  saved = windows.num_saved
+  if step_weights is None:
+    return torch.full((saved,), 1.0 / saved, dtype=torch.float32, device=device)
+  return torch.as_tensor(step_weights, dtype=torch.float32).to(device).contiguous()
+
+
+def _rollout_minibatches(sample_index, num_steps: int, replicas: int, windows, device):
+  """sample_index of a rollout run as a contiguous int32 device tensor [K, batch] or
+  [K, R, batch]; None: every step trains on all windows."""
+  import torch
+  if sample_index is None:
+    sample_index = torch.arange(windows.num_windows, dtype=torch.int32).repeat(num_steps, 1)
+  sample_index = torch.as_tensor(sample_index, dtype=torch.int32).to(device).contiguous()
+  if (sample_index.dim() not in (2, 3) or int(sample_index.shape[0]) != num_steps or
+      (sample_index.dim() == 3 and int(sample_index.shape[1]) != replicas)):
+    raise ValueError('sample_index must be [num_steps, batch] or [num_steps, R, batch]')
+  return sample_index
+
+
 class RolloutTrainer(object):
   """Training on rollout error (ddd_train_rollout_loss_grad, csrc/train_rollout.hip): the
   flat weight vector, null spaces and Adam(beta2 = 0.99) of Trainer; the loss is
   sum_j step_weights[j] step_means[j] over the saved steps of RolloutWindows, its gradient
   one launch.  clip_norm: the gradient is rescaled to that global norm where it exceeds
-  it, on the device."""
+  it, on the device.  `run` hands a whole stretch of steps to the device
+  (ddd_train_rollout_run, csrc/train_rollout_population.hip, as the population of one)."""
 
   def __init__(self, model: model_lib.LearnedStencilModel, hparams=None, clip_norm=None):
     hparams = hparams or model.hparams
@@ -393,13 +421,7 @@ class RolloutTrainer(object):
     `sample_index` (int32 device tensor; None: all).  step_weights: [num_saved] host or
     device values c_j, 1 / num_saved each by default."""
     torch = self.torch
-    saved = windows.num_saved
-    if step_weights is None:
-      step_weights = torch.full((saved,), 1.0 / saved, dtype=torch.float32,
-                                device=self.weights.device)
-    else:
-      step_weights = torch.as_tensor(step_weights, dtype=torch.float32).to(
-          self.weights.device).contiguous()
+    step_weights = _rollout_step_weights(windows, step_weights, self.weights.device)
     batch = windows.num_windows if sample_index is None else int(sample_index.shape[0])
     need = _lib.load_library().ddd_train_rollout_workspace_bytes(
         self.cfg, batch, windows.num_steps)
@@ -432,22 +454,72 @@ class RolloutTrainer(object):
     self.step_count += 1
     return means
 
+  def run(self, windows: RolloutWindows, num_steps: int, lr, sample_index,
+          step_weights=None):
+    """num_steps optimiser steps in one ddd_train_rollout_run call, as the population of
+    one on this trainer's weights: the gradient of `step`, the norm, the skip of a step
+    whose gradient is not finite, the clip and Adam on the device; the host reads once,
+    after the call.  lr: one rate or one per step; sample_index: int32 [num_steps, batch]
+    (None: all windows every step).  Returns step_means [num_steps, num_saved] (device).
+    Shares the optimiser state with `step`, so the two may be interleaved; skipped steps
+    are counted in skipped_steps and not in step_count, as `step` counts them."""
+    torch = self.torch
+    num_steps = int(num_steps)
+    if num_steps < 1:
+      raise ValueError('num_steps = {} (>= 1)'.format(num_steps))
+    rates = ([float(lr)] * num_steps if np.isscalar(lr) else [float(rate) for rate in lr])
+    if len(rates) != num_steps:
+      raise ValueError('lr must be one rate or one per step')
+    device = self.weights.device
+    sample_index = _rollout_minibatches(sample_index, num_steps, 1, windows, device)
+    state = self._base._adam_state()
+    group = self.optimizer.param_groups[0]
+    adam_step = torch.tensor([int(state['step'])], dtype=torch.int32, device=device)
+    log, norms, _ = _lib.train_rollout_run(
+        self.cfg, self.weights.detach()[None], state['exp_avg'][None],
+        state['exp_avg_sq'][None], adam_step, windows.y0, windows.targets,
+        _rollout_step_weights(windows, step_weights, device), windows.num_steps,
+        windows.save_every, windows.dt, sample_index, [rates], betas=group['betas'],
+        epsilon=group['eps'], clip_norm=self.clip_norm or 0.0, t0=windows.t0,
+        forcing=windows.forcing, nullspace=self.nullspace, bias=self.bias)
+    skipped = int((~torch.isfinite(norms)).sum())   # (the one host read of the run)
+    state['step'] += num_steps - skipped
+    group['lr'] = rates[-1]
+    self.step_count += num_steps - skipped
+    self.skipped_steps += skipped
+    return log[:, 0]
+
   def export(self) -> model_lib.LearnedStencilModel:
     """The current weights as a LearnedStencilModel (same equation / hparams)."""
     return self._base.export()
 
 
+def _rollout_stretches(opt_steps: int, step: int, eval_interval: int):
+  """The lengths of the stretches between two evaluations of a horizon of opt_steps steps
+  that begins at global step `step`: an evaluation follows every eval_interval-th global
+  step and the horizon's last step."""
+  lengths, begun = [], 0
+  for k in range(opt_steps):
+    if (step + k + 1) % eval_interval == 0 or k == opt_steps - 1:
+      lengths.append(k + 1 - begun)
+      begun = k + 1
+  return lengths
+
+
 def fine_tune_on_rollouts(model: model_lib.LearnedStencilModel, y_exact, times, hparams,
                           checkpoint_dir: str, horizons, save_every: int, batch: int,
                           learning_rate: float, seed: int = 0, stride: int = 1,
-                          first_seed: int = 0, clip_norm=None) -> List[Dict[str, float]]:
+                          first_seed: int = 0, clip_norm=None,
+                          fused: bool = False) -> List[Dict[str, float]]:
   """A curriculum of growing horizons over one RolloutTrainer: for every (opt_steps,
   num_steps) of `horizons`, opt_steps optimiser steps on seeded minibatches of `batch`
   windows of num_steps model steps (make_rollout_windows of y_exact / times).  Writes
   hparams.json + model.npz to checkpoint_dir.  Returns one row at the start of every
   horizon, at every hparams.eval_interval-th step and at the end of every horizon:
   'step' (over all horizons), 'num_steps', 'loss' and 'step_means' over ALL windows of
-  that horizon (forward only, uniform step weights), and 'skipped_steps' so far."""
+  that horizon (forward only, uniform step weights), and 'skipped_steps' so far.
+  fused: every stretch between two evaluations is one RolloutTrainer.run call (the same
+  minibatches) instead of RolloutTrainer.step calls."""
   hparams = copy.deepcopy(hparams)
   trainer = RolloutTrainer(model, hparams, clip_norm=clip_norm)
   torch = trainer.torch
@@ -467,6 +539,14 @@ def fine_tune_on_rollouts(model: model_lib.LearnedStencilModel, y_exact, times, 
                                    stride=stride, first_seed=first_seed)
     count = min(int(batch), windows.num_windows)
     evaluate(windows)
+    if fused:
+      for length in _rollout_stretches(int(opt_steps), step, hparams.eval_interval):
+        index = np.stack([rs.choice(windows.num_windows, size=count, replace=False)
+                          .astype(np.int32) for _ in range(length)])
+        trainer.run(windows, length, learning_rate, index)
+        step += length
+        evaluate(windows)
+      continue
     for k in range(int(opt_steps)):
       index = torch.as_tensor(rs.choice(windows.num_windows, size=count, replace=False)
                               .astype(np.int32), device=trainer.weights.device)
@@ -476,6 +556,27 @@ def fine_tune_on_rollouts(model: model_lib.LearnedStencilModel, y_exact, times, 
         evaluate(windows)
   trainer.export().save(checkpoint_dir)
   return rows
+
+
+def _checked_population(models, hparams, checker) -> list:
+  """What PopulationTrainer and RolloutPopulationTrainer refuse before any device work: a
+  replica count outside 1 .. DDD_MAX_REPLICAS, hparams that `checker` raises for, and
+  replicas that differ in their equation, architecture or grid.  Returns list(models)."""
+  models = list(models)
+  if not 1 <= len(models) <= _lib.MAX_REPLICAS:
+    raise ValueError('{} models (1 .. {})'.format(len(models), _lib.MAX_REPLICAS))
+  checker(hparams)
+  configs = [bytes(_train_config(model)) for model in models]
+  for r, model in enumerate(models):
+    if type(model.equation) is not type(models[0].equation):
+      raise ValueError('replica {} solves {}, replica 0 {}: one equation per '
+                       'population'.format(r, type(model.equation).__name__,
+                                           type(models[0].equation).__name__))
+    if (configs[r] != configs[0] or [w.shape for w in model.conv_kernels] !=
+        [w.shape for w in models[0].conv_kernels]):
+      raise ValueError('replica {} differs from replica 0 in its architecture or grid: '
+                       'one architecture per population'.format(r))
+  return models
 
 
 class PopulationTrainer(object):
@@ -491,20 +592,7 @@ class PopulationTrainer(object):
 
   def __init__(self, models: Sequence[model_lib.LearnedStencilModel], hparams,
                learning_rates=None):
-    models = list(models)
-    if not 1 <= len(models) <= _lib.MAX_REPLICAS:
-      raise ValueError('{} models (1 .. {})'.format(len(models), _lib.MAX_REPLICAS))
-    _checker(hparams)(hparams)
-    configs = [bytes(_train_config(model)) for model in models]
-    for r, model in enumerate(models):
-      if type(model.equation) is not type(models[0].equation):
-        raise ValueError('replica {} solves {}, replica 0 {}: one equation per '
-                         'population'.format(r, type(model.equation).__name__,
-                                             type(models[0].equation).__name__))
-      if (configs[r] != configs[0] or [w.shape for w in model.conv_kernels] !=
-          [w.shape for w in models[0].conv_kernels]):
-        raise ValueError('replica {} differs from replica 0 in its architecture or grid: '
-                         'one architecture per population'.format(r))
+    models = _checked_population(models, hparams, _checker(hparams))
     if learning_rates is not None:
       learning_rates = [[float(rate) for rate in row] for row in learning_rates]
       if len(learning_rates) != len(models):
@@ -604,6 +692,149 @@ class PopulationTrainer(object):
     if self._rollout_population is None:
       self._rollout_population = evaluation.RolloutPopulation(self.models[0], self.replicas)
     return self._rollout_population.load(self.weights)
+
+  def rollout_trainer(self, clip_norm=None) -> 'RolloutPopulationTrainer':
+    """A RolloutPopulationTrainer on this population's `weights` tensor (the same storage:
+    what it trains, rollout_population() and export() see) with a fresh Adam state, so that
+    training_population -> rollout fine-tuning -> rollout scoring never leaves the device."""
+    return RolloutPopulationTrainer(self.models, self.hparams, clip_norm=clip_norm,
+                                    population=self)
+
+
+class RolloutPopulationTrainer(object):
+  """R replicas of one architecture fine-tuned together on rollout error
+  (ddd_train_rollout_run, csrc/train_rollout_population.hip): `weights`, `adam_m`, `adam_v`
+  [R, n_weights] and `adam_steps` int32 [R] (the updates each replica has applied) on the
+  device, Adam(beta2 = 0.99) and clip_norm as RolloutTrainer.  A step whose gradient is not
+  finite is skipped for that replica alone and counted in skipped_steps [R].  Replica r of
+  `run` is bit for bit the population of one on models[r].  population: the
+  PopulationTrainer whose weights to train in place (PopulationTrainer.rollout_trainer)."""
+
+  BETAS = PopulationTrainer.BETAS
+  EPSILON = PopulationTrainer.EPSILON
+
+  def __init__(self, models: Sequence[model_lib.LearnedStencilModel], hparams,
+               clip_norm=None, population: PopulationTrainer = None):
+    single = copy.copy(hparams)   # (the horizon is the windows', not num_time_steps)
+    single.num_time_steps = 0
+    models = _checked_population(models, single, check_supported)
+    if population is None:
+      population = PopulationTrainer(models, hparams)
+    torch = population.torch
+    self.torch = torch
+    self.population = population
+    self.models, self.hparams, self.cfg = models, hparams, population.cfg
+    self.nullspace, self.bias = population.nullspace, population.bias
+    self.weights = population.weights
+    self.adam_m = torch.zeros_like(self.weights)
+    self.adam_v = torch.zeros_like(self.weights)
+    self.adam_steps = torch.zeros(len(models), dtype=torch.int32, device=self.weights.device)
+    self.clip_norm = None if clip_norm is None else float(clip_norm)
+    self.skipped_steps = np.zeros(len(models), np.int64)
+    self._workspace = None
+
+  @property
+  def replicas(self) -> int:
+    return len(self.models)
+
+  def _call(self, windows, sample_index, rates, step_weights, forward_only):
+    torch = self.torch
+    device = self.weights.device
+    batch = windows.num_windows if sample_index is None else int(sample_index.shape[-1])
+    need = _lib.load_library().ddd_train_rollout_run_workspace_bytes(
+        self.cfg, batch, windows.num_steps, self.replicas)
+    if self._workspace is None or self._workspace.numel() < need:
+      self._workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    return _lib.train_rollout_run(
+        self.cfg, self.weights, self.adam_m, self.adam_v, self.adam_steps, windows.y0,
+        windows.targets, _rollout_step_weights(windows, step_weights, device),
+        windows.num_steps, windows.save_every, windows.dt, sample_index, rates,
+        betas=self.BETAS, epsilon=self.EPSILON, clip_norm=self.clip_norm or 0.0,
+        t0=windows.t0, forcing=windows.forcing, nullspace=self.nullspace, bias=self.bias,
+        forward_only=forward_only, workspace=self._workspace)
+
+  def run(self, windows: RolloutWindows, num_steps: int, learning_rates, sample_index=None,
+          step_weights=None):
+    """num_steps optimiser steps of every replica in one call.  learning_rates: one rate,
+    one per replica [R] or one per replica and step [R][num_steps]; sample_index: int32
+    [num_steps, batch] (shared) or [num_steps, R, batch] (None: all windows every step).
+    Returns, after one host read, (step_means [num_steps, R, num_saved], grad_norms
+    [num_steps, R]) as float32 host arrays; a norm that is not finite marks a skipped step
+    and is counted in skipped_steps."""
+    torch = self.torch
+    num_steps, R = int(num_steps), self.replicas
+    if num_steps < 1:
+      raise ValueError('num_steps = {} (>= 1)'.format(num_steps))
+    rates = np.asarray(learning_rates, np.float64)
+    if rates.ndim == 1 and rates.shape[0] == R:
+      rates = rates[:, None]
+    if rates.ndim not in (0, 2) or (rates.ndim == 2 and (
+        rates.shape[0] != R or rates.shape[1] not in (1, num_steps))):
+      raise ValueError('learning_rates must be one rate, [R] or [R][num_steps]')
+    rates = np.broadcast_to(rates, (R, num_steps)).tolist()
+    sample_index = _rollout_minibatches(sample_index, num_steps, R, windows,
+                                        self.weights.device)
+    log, norms, _ = self._call(windows, sample_index, rates, step_weights, False)
+    both = torch.cat([log, norms[..., None]], dim=-1).cpu().numpy()   # (the one host read)
+    means, norms = both[..., :-1], both[..., -1]
+    self.skipped_steps += (~np.isfinite(norms)).sum(axis=0)
+    return means, norms
+
+  def loss(self, windows: RolloutWindows, step_weights=None) -> np.ndarray:
+    """step_means [R, num_saved] float64 over ALL windows, forward only: one call and one
+    host read for all replicas; row r is bit for bit the step_means of a forward-only
+    ddd_train_rollout_loss_grad call on replica r."""
+    log, _, _ = self._call(windows, None, None, step_weights, True)
+    return log[0].double().cpu().numpy()
+
+  def export(self) -> List[model_lib.LearnedStencilModel]:
+    """The current weights as R LearnedStencilModels."""
+    return self.population.export()
+
+
+def fine_tune_population_on_rollouts(models: Sequence[model_lib.LearnedStencilModel], y_exact,
+                                     times, hparams, checkpoint_dirs: Sequence[str], horizons,
+                                     save_every: int, batch: int, learning_rates,
+                                     seed: int = 0, stride: int = 1, first_seed: int = 0,
+                                     clip_norm=None) -> List[List[Dict[str, float]]]:
+  """fine_tune_on_rollouts(..., seed=seed, fused=True) for R replicas at once: the same
+  curriculum, windows and minibatch order (shared by the replicas), replica r at
+  learning_rates[r]; every stretch between two evaluations is one
+  RolloutPopulationTrainer.run, every evaluation one forward-only call for all replicas.
+  Writes hparams.json + model.npz to checkpoint_dirs[r]; returns one list of rows per
+  replica, with fine_tune_on_rollouts' keys."""
+  models = list(models)
+  learning_rates = [float(rate) for rate in learning_rates]
+  if len(checkpoint_dirs) != len(models) or len(learning_rates) != len(models):
+    raise ValueError('one checkpoint directory and one learning rate per model')
+  hparams = copy.deepcopy(hparams)
+  trainer = RolloutPopulationTrainer(models, hparams, clip_norm=clip_norm)
+  for checkpoint_dir in checkpoint_dirs:
+    os.makedirs(checkpoint_dir, exist_ok=True)
+    hparams_lib.save_hparams(hparams, checkpoint_dir)
+  rs = np.random.RandomState(seed)
+  rows, step = [[] for _ in models], 0
+
+  def evaluate(windows):
+    for r, means in enumerate(trainer.loss(windows)):
+      rows[r].append({'step': step, 'num_steps': windows.num_steps,
+                      'loss': float(means.mean()), 'step_means': means.tolist(),
+                      'skipped_steps': int(trainer.skipped_steps[r])})
+
+  for opt_steps, num_steps in horizons:
+    windows = make_rollout_windows(y_exact, times, hparams, num_steps, save_every,
+                                   stride=stride, first_seed=first_seed)
+    count = min(int(batch), windows.num_windows)
+    evaluate(windows)
+    for length in _rollout_stretches(int(opt_steps), step, hparams.eval_interval):
+      index = np.stack([rs.choice(windows.num_windows, size=count, replace=False)
+                        .astype(np.int32) for _ in range(length)])
+      trainer.run(windows, length, learning_rates, index)
+      step += length
+      evaluate(windows)
+  for model, checkpoint_dir in zip(trainer.export(), checkpoint_dirs):
+    model.save(checkpoint_dir)
+  return rows
 
 
 def _scaled_loss_per_head(sums, hparams) -> np.ndarray:

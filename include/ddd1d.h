@@ -753,6 +753,97 @@ DDD_API size_t ddd_train_population_workspace_bytes(const ddd_config* cfg, int b
 DDD_API int ddd_train_population_run(const ddd_config* cfg,
                                      const ddd_train_population_args* args, void* stream);
 
+/* ---- rollout fine-tuning on the device, for replica populations --------------
+ * Replaces: num_opt_steps iterations of training.RolloutTrainer.step per replica:
+ * per step the loss and gradient of ddd_train_rollout_loss_grad on that step's
+ * minibatch of windows, the gradient's global norm, the skip of a step whose
+ * norm is not finite, the rescaling to clip_norm and Adam, for R replicas of one
+ * architecture over one set of windows.  One call enqueues every step on `stream`
+ * and returns: no stream synchronisation, no copy to the host, no graph capture.
+ * A step is four launches whatever R is (the replicas are a second grid dimension),
+ * and each replica keeps the workgroups, slabs and summation order of a solo run:
+ *   - the gradient of a step (last_grad) and its step means are bit for bit what
+ *     ddd_train_rollout_loss_grad returns for the same weights and minibatch;
+ *   - norm = sqrt(sum g^2), summed in float64 in a fixed order; grad_norm_log holds
+ *     (float) norm, before clipping.  Not finite: the step is SKIPPED for this
+ *     replica: weights, adam_m, adam_v and adam_step keep their bits;
+ *   - otherwise g' = g * (float) min(1, clip_norm / (norm + 1e-12)) (clip_norm = 0:
+ *     g' = g), t = ++adam_step[r], and the update of ddd_train_run in float32:
+ *       m += (g' - m) (1 - beta1);  v = beta2 v + (1 - beta2) g'^2;
+ *       denom = sqrt(v) / sqrt(1 - beta2^t) + epsilon;  w -= (lr / (1 - beta1^t)) m / denom
+ *     lr / (1 - beta1^t) and sqrt(1 - beta2^t) are formed ON THE DEVICE in double and
+ *     rounded to float: skips are per replica and decided there, so t lives on the
+ *     device.  The device's pow may differ from the host's by an ulp of double; what
+ *     is bit for bit is so between runs on the device: replica r of a call equals
+ *     the call with that replica alone (weights, adam_m, adam_v, adam_step, every
+ *     log row and last_grad), K steps in one call equal the same steps in several.
+ * An index outside [0, S) makes that step's means and gradient NaN for the
+ * replicas that read it, which skips their step.  Supports exactly the
+ * configurations ddd_train_rollout_loss_grad supports and refuses the others with
+ * the same status and text ("ddd_train_rollout_run" as the entry point's name).
+ * DDD_ERR_INVALID_ARGUMENT: a struct_size mismatch; replicas, num_opt_steps,
+ * num_steps or save_every out of range; dt <= 0; clip_norm negative or not finite;
+ * a beta outside [0, 1); epsilon <= 0; a learning rate negative or not finite; a
+ * required pointer NULL; forcing pointers partly given; a workspace too small.
+ *
+ * forward_only = 1 (num_opt_steps must be 1): one loss pass without gradient per
+ * replica fills step_means_log[0]; nothing else is written.  sample_index may be
+ * NULL (all rows, batch = num_rows); learning_rate, adam_* and grad_norm_log may
+ * be NULL. */
+typedef struct ddd_train_rollout_run_args {
+  int32_t struct_size;   /* = sizeof(ddd_train_rollout_run_args), checked */
+  int32_t batch;         /* windows per minibatch */
+  int32_t num_rows;      /* S: rows of y0 / targets / t0 / the forcing tables */
+  int32_t num_steps;     /* T in [1, DDD_MAX_ROLLOUT_STEPS] */
+  int32_t save_every;    /* a divisor of T; T / save_every saved steps */
+  int32_t num_opt_steps; /* K >= 1: optimiser steps of this call */
+  int32_t replicas;      /* R in [1, DDD_MAX_REPLICAS] */
+  int32_t index_per_replica; /* 0: one minibatch order for all; 1: one per replica */
+  int32_t forward_only;  /* 0 or 1 */
+  float* weights;        /* in/out [R][n_weights] (ddd_model_create layout per row) */
+  float* adam_m;         /* in/out [R][n_weights] */
+  float* adam_v;         /* in/out [R][n_weights] */
+  int32_t* adam_step;    /* in/out DEVICE [R]: updates applied so far (>= 0) */
+  const float* nullspace; /* as ddd_train_args */
+  const float* bias;     /* as ddd_train_args */
+  /* the windows, shared by all replicas, as in ddd_train_rollout_args */
+  const float* y0;       /* device [S][N] */
+  const float* targets;  /* device [S][T / save_every][N] */
+  const float* step_weights; /* device [T / save_every] */
+  double dt;
+  const double* t0;      /* device [S] or NULL (0) */
+  int32_t nparams, n_k;
+  const float* amplitude;     /* [S][nparams]; all five NULL = unforced */
+  const float* omega;         /* [S][nparams] */
+  const float* phase;         /* [S][nparams] */
+  const int32_t* k_index;     /* [S][nparams] */
+  const float* spatial_phase; /* [n_k][N] */
+  const int32_t* sample_index; /* device [K][batch], or [K][R][batch] with
+                                  index_per_replica */
+  const double* learning_rate; /* HOST [R][K], finite and >= 0 */
+  double beta1, beta2;   /* in [0, 1) */
+  double epsilon;        /* > 0 */
+  double clip_norm;      /* >= 0, finite; 0 = no clipping */
+  float* step_means_log; /* out [K][R][T / save_every] */
+  float* grad_norm_log;  /* out [K][R]: the norm before clipping; not finite = the
+                            step was skipped */
+  float* last_grad;      /* out [R][n_weights] or NULL: the last step's gradients,
+                            before clipping */
+  void* workspace;       /* ddd_train_rollout_run_workspace_bytes(cfg, batch, T, R) bytes */
+  size_t workspace_bytes;
+} ddd_train_rollout_run_args;
+
+/* Bytes of the caller-allocated workspace of ddd_train_rollout_run: `replicas` times
+ * ddd_train_rollout_workspace_bytes(cfg, batch, T), then the gradient buffers, the
+ * partial sums of the norms and the decision records.  Depends only on cfg, batch, T
+ * and R.  0 on error, replicas outside [1, DDD_MAX_REPLICAS] included. */
+DDD_API size_t ddd_train_rollout_run_workspace_bytes(const ddd_config* cfg, int batch,
+                                                     int num_steps, int replicas);
+/* Enqueues num_opt_steps optimiser steps of every replica (or the forward-only pass).
+ * Arguments are checked before any device work. */
+DDD_API int ddd_train_rollout_run(const ddd_config* cfg,
+                                  const ddd_train_rollout_run_args* args, void* stream);
+
 /* ---- evaluation on the device -----------------------------------------------
  * Replaces: training.Inferer.run + calculate_metrics (training.py:253-314,
  * 433-491) for R replicas of one architecture over one dataset: forward only,
