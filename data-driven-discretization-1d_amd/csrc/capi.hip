@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/ddd1d.h"
+#include "capi_common.h"
 #include "dev_params.h"
 #include "launch.h"
 #include "launch_weno.h"
@@ -36,17 +37,46 @@
 #include "rhs_stream.h"
 #include "ring_args.h"
 #include "rollout_scores.h"
-#include "train.h"
-#include "train_metrics.h"
-#include "train_population.h"
-#include "train_rollout.h"
-#include "train_rollout_population.h"
-#include "train_unrolled.h"
 #include "rhs_weno.h"   // (host side only: weno::supports; the kernels are weno_unit.hip)
 
-namespace {
+// What capi_train.hip shares (capi_common.h)
+namespace ddd {
+namespace capi {
 
 thread_local std::string g_error;
+
+int fail(int code, const char* fmt, ...) {
+  char buf[1024];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  g_error = buf;
+  return code;
+}
+
+bool is_conservative(int eq) {
+  switch (eq) {
+    case DDD_EQ_BURGERS_CONSERVATIVE: case DDD_EQ_KDV_CONSERVATIVE:
+    case DDD_EQ_KS_CONSERVATIVE: case DDD_EQ_BURGERS_GODUNOV:
+    case DDD_EQ_KDV_GODUNOV: case DDD_EQ_KS_GODUNOV:
+      return true;
+    default:
+      return false;
+  }
+}
+
+bool is_forced_family(int eq) {   // equations.py:276-277: only Burgers adds forcing(t)
+  return eq == DDD_EQ_BURGERS || eq == DDD_EQ_BURGERS_CONSERVATIVE ||
+         eq == DDD_EQ_BURGERS_GODUNOV;
+}
+
+}  // namespace capi
+}  // namespace ddd
+
+using namespace ddd::capi;
+
+namespace {
 
 // Profiling / A-B switches.  The product library (libddd1d.so) has none: the
 // struct below is constant there and every test on it folds away.  In
@@ -76,24 +106,6 @@ DebugOptions g_debug;
 constexpr DebugOptions g_debug{};
 #endif
 
-int fail(int code, const char* fmt, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_error = buf;
-  return code;
-}
-
-#define DDD_HIP(expr)                                                        \
-  do {                                                                       \
-    hipError_t err__ = (expr);                                               \
-    if (err__ != hipSuccess)                                                 \
-      return fail(DDD_ERR_HIP, "%s failed: %s (%s:%d)", #expr,              \
-                  hipGetErrorString(err__), __FILE__, __LINE__);             \
-  } while (0)
-
 template <typename T>
 int upload(const std::vector<T>& host, T** dev) {
   *dev = nullptr;
@@ -102,22 +114,6 @@ int upload(const std::vector<T>& host, T** dev) {
   DDD_HIP(hipMemcpy(*dev, host.data(), host.size() * sizeof(T),
                     hipMemcpyHostToDevice));
   return DDD_OK;
-}
-
-bool is_conservative(int eq) {
-  switch (eq) {
-    case DDD_EQ_BURGERS_CONSERVATIVE: case DDD_EQ_KDV_CONSERVATIVE:
-    case DDD_EQ_KS_CONSERVATIVE: case DDD_EQ_BURGERS_GODUNOV:
-    case DDD_EQ_KDV_GODUNOV: case DDD_EQ_KS_GODUNOV:
-      return true;
-    default:
-      return false;
-  }
-}
-
-bool is_forced_family(int eq) {   // equations.py:276-277: only Burgers adds forcing(t)
-  return eq == DDD_EQ_BURGERS || eq == DDD_EQ_BURGERS_CONSERVATIVE ||
-         eq == DDD_EQ_BURGERS_GODUNOV;
 }
 
 int expected_derivatives(int eq) {
@@ -383,11 +379,7 @@ struct ddd_model {
   size_t scratch_floats = 0;
 };
 
-namespace {
-
-void free_dev(void* p) { if (p) (void)hipFree(p); }
-
-int common_config_checks(const ddd_config* cfg) {
+int ddd::capi::common_config_checks(const ddd_config* cfg) {
   if (cfg == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "cfg is NULL");
   if (cfg->struct_size != (int32_t)sizeof(ddd_config))
     return fail(DDD_ERR_INVALID_ARGUMENT,
@@ -408,6 +400,10 @@ int common_config_checks(const ddd_config* cfg) {
                 cfg->stencil_size, DDD_MAX_STENCIL);
   return DDD_OK;
 }
+
+namespace {
+
+void free_dev(void* p) { if (p) (void)hipFree(p); }
 
 // rhs_mfma.h replaces u / stddev by q' = fma(fma(-q, s, u), r, q), q = RN(u r),
 // r = RN(1 / s).  True for every float32 u iff it is true for the 2^23
@@ -1340,521 +1336,6 @@ int substep_entry(ddd_model* m, const ddd::SubstepArgs& a, hipStream_t stream) {
     ch.forked = false;
   }
   return rc;
-}
-
-
-// ---- training (train.h) ----------------------------------------------------
-// The configuration checks of ddd_train_workspace_bytes / ddd_train_loss_grad (and of
-// ddd_vjp_workspace_bytes / ddd_result_vjp, which admit the same configurations) and the
-// kernel parameters they imply (everything but the argument pointers).  `who` names the
-// entry point in the messages of what is not supported.
-int train_params(const ddd_config* cfg, int batch, ddd::train::TrainParams* tp, int* blocks,
-                 size_t* ws_bytes, size_t* lds_bytes, const char* who = "training") {
-  int rc = common_config_checks(cfg);
-  if (rc) return rc;
-  if (cfg->equation > DDD_EQ_KS_CONSERVATIVE)
-    return fail(DDD_ERR_UNSUPPORTED,
-                "%s: equation %d (numerical_flux / Godunov equations) is not supported", who,
-                cfg->equation);
-  if (cfg->model_target == DDD_TARGET_FLUX)
-    return fail(DDD_ERR_UNSUPPORTED, "%s: model_target 'flux' is not supported", who);
-  if (cfg->model_target < DDD_TARGET_COEFFICIENTS || cfg->model_target > DDD_TARGET_FLUX)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "unknown model_target %d", cfg->model_target);
-  if (cfg->num_layers < 1)
-    return fail(DDD_ERR_UNSUPPORTED, "%s: num_layers = %d (a net without conv layers "
-                "has no conv weights to train)", who, cfg->num_layers);
-  if (cfg->num_layers > DDD_MAX_LAYERS)
-    return fail(DDD_ERR_UNSUPPORTED, "%s: num_layers = %d > %d", who, cfg->num_layers,
-                DDD_MAX_LAYERS);
-  if (cfg->kernel_size < 1 || cfg->kernel_size > 7)
-    return fail(DDD_ERR_UNSUPPORTED, "%s: kernel_size = %d out of range [1, 7]", who,
-                cfg->kernel_size);
-  if (cfg->filter_size < 1 || cfg->filter_size > 64)
-    return fail(DDD_ERR_UNSUPPORTED, "%s: filter_size = %d out of range [1, 64]", who,
-                cfg->filter_size);
-  if (cfg->num_points < 8 || cfg->num_points > 256)
-    return fail(DDD_ERR_UNSUPPORTED, "%s: num_points = %d out of range [8, 256]", who,
-                cfg->num_points);
-  if (cfg->activation < DDD_ACT_RELU || cfg->activation > DDD_ACT_ELU)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "unknown activation %d", cfg->activation);
-  if (!(cfg->standard_deviation > 0.0))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "standard_deviation must be positive");
-  if (cfg->polynomial_accuracy_order < 0)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "polynomial_accuracy_order = %d",
-                cfg->polynomial_accuracy_order);
-  if (batch < 1) return fail(DDD_ERR_INVALID_ARGUMENT, "batch = %d", batch);
-
-  ddd::train::TrainParams& p = *tp;
-  std::memset(&p, 0, sizeof(p));
-  p.equation = cfg->equation;
-  p.N = cfg->num_points;
-  p.D = cfg->num_derivatives;
-  p.G = cfg->stencil_size;
-  p.H = p.D + 1;
-  p.target = cfg->model_target;
-  p.L = cfg->num_layers;
-  p.K = cfg->kernel_size;
-  p.act = cfg->activation;
-  p.pao = cfg->model_target == DDD_TARGET_COEFFICIENTS ? cfg->polynomial_accuracy_order : 0;
-  p.unbiased = cfg->ensure_unbiased_coefficients ? 1 : 0;
-  p.conservative = is_conservative(cfg->equation) ? 1 : 0;
-  p.eta = (float)cfg->eta;
-  p.stddev = (float)cfg->standard_deviation;
-  p.inv_dx = (float)(1.0 / cfg->dx);
-  if (p.unbiased && (p.target != DDD_TARGET_COEFFICIENTS || p.pao != 0))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ensure_unbiased_coefficients needs model_target 'coefficients' with "
-                "polynomial_accuracy_order = 0");
-  if (p.unbiased)
-    for (int d = 0; d < p.D; ++d)
-      if (cfg->derivative_orders[d] == 0)
-        return fail(DDD_ERR_INVALID_ARGUMENT,
-                    "ensure_unbiased not yet supported for 0th order spatial derivatives");
-  int c_out = 1;
-  if (p.target == DDD_TARGET_COEFFICIENTS) {
-    if (p.pao > 0) {
-      c_out = 0;
-      for (int d = 0; d < p.D; ++d) {
-        if (cfg->input_sizes[d] < 1 || cfg->input_sizes[d] > p.G)
-          return fail(DDD_ERR_INVALID_ARGUMENT, "input_sizes[%d] = %d out of range [1, G]", d,
-                      cfg->input_sizes[d]);
-        p.in_start[d] = c_out;
-        p.in_size[d] = cfg->input_sizes[d];
-        p.ns_off[d] = c_out * p.G;
-        c_out += cfg->input_sizes[d];
-      }
-    } else {
-      c_out = p.D * p.G;
-    }
-  } else if (p.target == DDD_TARGET_SPACE_DERIVATIVES) {
-    c_out = p.D;
-  }
-  p.C_out = c_out;
-  size_t off = 0, zoff = 0;
-  p.cmax = 1;
-  for (int l = 0; l < p.L; ++l) {
-    p.cin[l] = l == 0 ? 1 : cfg->filter_size;
-    p.cout[l] = l == p.L - 1 ? c_out : cfg->filter_size;
-    p.cmax = std::max(p.cmax, std::max(p.cin[l], p.cout[l]));
-    p.w_off[l] = (int)off;
-    off += (size_t)p.K * p.cin[l] * p.cout[l] + p.cout[l];
-    p.z_off[l] = (int)zoff;
-    if (l < p.L - 1) zoff += (size_t)p.N * p.cout[l];
-  }
-  p.n_weights = (int)off;
-  p.n_slab = (int)((off + 2 * p.H + 3) & ~(size_t)3);
-  p.slab_stride = (size_t)p.n_slab + ((zoff + 3) & ~(size_t)3);
-  p.batch = batch;
-  *blocks = std::min(batch, ddd::train::kMaxBlocks);
-  *ws_bytes = (size_t)*blocks * p.slab_stride * sizeof(float);
-  // the 32 -> 32 layers on MFMA (train.hip) where N is a multiple of 32 and the staged
-  // kernels fit next to the rest; otherwise every layer on the VALU
-  p.mfma = 0;
-  p.wl_floats = 0;
-  for (int l = 0; l < p.L; ++l) p.wl_off[l] = -1;
-  if (p.N % 32 == 0) {
-    int staged = 0;
-    for (int l = 0; l < p.L; ++l)
-      if (p.cin[l] == 32 && p.cout[l] == 32) {
-        p.wl_off[l] = staged;
-        staged += p.K * 32 * 32;
-      }
-    if (staged > 0 && (ddd::train::lds_floats(p) + staged) * sizeof(float) <= 160 * 1024) {
-      p.mfma = 1;
-      p.wl_floats = staged;
-    } else {
-      for (int l = 0; l < p.L; ++l) p.wl_off[l] = -1;
-    }
-  }
-  *lds_bytes = ddd::train::lds_total_floats(p) * sizeof(float);
-  if (*lds_bytes > 160 * 1024)
-    return fail(DDD_ERR_UNSUPPORTED, "%s: %zu bytes of LDS needed (> 160 KiB)", who,
-                *lds_bytes);
-  return DDD_OK;
-}
-
-static_assert(ddd::train::kMaxTimeSteps == DDD_MAX_TIME_STEPS, "train_unrolled.h / ddd1d.h");
-static_assert(ddd::train::kMaxUnrolledHeads == DDD_MAX_UNROLLED_HEADS, "train_unrolled.h / ddd1d.h");
-
-// train_params for ddd_train_unrolled_loss_grad (train_unrolled.h): the same checks and
-// messages, then num_time_steps, the wider head part of a slab, the stage states and the
-// integrated heads' cotangents behind the pre-activations, and two more LDS rows under
-// the same 160 KiB check (the staged MFMA kernels are dropped first when they no longer fit).
-int train_unrolled_params(const ddd_config* cfg, int batch, int num_time_steps,
-                          ddd::train::UnrolledParams* up, int* blocks, size_t* ws_bytes,
-                          size_t* lds_bytes, const char* who = "training") {
-  std::memset(up, 0, sizeof(*up));
-  ddd::train::TrainParams& p = up->t;
-  int rc = train_params(cfg, batch, &p, blocks, ws_bytes, lds_bytes, who);
-  if (rc) return rc;
-  if (num_time_steps < 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "num_time_steps = %d (>= 1; ddd_train_loss_grad "
-                "carries the loss without integrated heads)", num_time_steps);
-  if (num_time_steps > DDD_MAX_TIME_STEPS)
-    return fail(DDD_ERR_UNSUPPORTED, "%s: num_time_steps = %d > %d", who, num_time_steps,
-                DDD_MAX_TIME_STEPS);
-  const int T = num_time_steps;
-  up->T = T;
-  up->HT = p.H + T;
-  const size_t z_floats = p.slab_stride - (size_t)p.n_slab;
-  p.n_slab = (int)(((size_t)p.n_weights + 2 * up->HT + 3) & ~(size_t)3);
-  up->st_off = (int)((size_t)p.n_slab + z_floats);
-  up->gi_off = up->st_off + 2 * T * p.N;
-  p.slab_stride = ((size_t)up->gi_off + (size_t)T * p.N + 3) & ~(size_t)3;
-  *ws_bytes = (size_t)*blocks * p.slab_stride * sizeof(float);
-  if (p.mfma && ddd::train::unrolled_lds_floats(p) * sizeof(float) > 160 * 1024) {
-    p.mfma = 0;
-    p.wl_floats = 0;
-    for (int l = 0; l < p.L; ++l) p.wl_off[l] = -1;
-  }
-  *lds_bytes = ddd::train::unrolled_lds_floats(p) * sizeof(float);
-  if (*lds_bytes > 160 * 1024)
-    return fail(DDD_ERR_UNSUPPORTED, "%s: %zu bytes of LDS needed (> 160 KiB)", who,
-                *lds_bytes);
-  return DDD_OK;
-}
-
-static_assert(ddd::train::kMaxRolloutSteps == DDD_MAX_ROLLOUT_STEPS, "train_rollout.h / ddd1d.h");
-
-// train_params for ddd_train_rollout_loss_grad (train_rollout.h) under that name (`who`:
-// ddd_train_rollout_run passes its own): the
-// same checks and messages, then num_steps.  A slab is laid out for save_every = 1 (the
-// workspace function does not know it): num_steps sums behind the gradient, then the
-// pre-activations, the 2 T stage states and up to T saved-step cotangents.  The LDS plan
-// and its 160 KiB check are train_unrolled_params'.
-int train_rollout_params(const ddd_config* cfg, int batch, int num_steps,
-                         ddd::train::RolloutParams* rp, int* blocks, size_t* ws_bytes,
-                         size_t* lds_bytes, const char* who = "ddd_train_rollout_loss_grad") {
-  std::memset(rp, 0, sizeof(*rp));
-  ddd::train::TrainParams& p = rp->t;
-  int rc = train_params(cfg, batch, &p, blocks, ws_bytes, lds_bytes, who);
-  if (rc) return rc;
-  if (num_steps < 1 || num_steps > DDD_MAX_ROLLOUT_STEPS)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "%s: num_steps = %d out of range [1, %d]", who,
-                num_steps, DDD_MAX_ROLLOUT_STEPS);
-  const int T = num_steps;
-  rp->T = T;
-  const size_t z_floats = p.slab_stride - (size_t)p.n_slab;
-  p.n_slab = (int)(((size_t)p.n_weights + T + 3) & ~(size_t)3);
-  rp->st_off = (int)((size_t)p.n_slab + z_floats);
-  rp->gi_off = rp->st_off + 2 * T * p.N;
-  p.slab_stride = ((size_t)rp->gi_off + (size_t)T * p.N + 3) & ~(size_t)3;
-  *ws_bytes = (size_t)*blocks * p.slab_stride * sizeof(float);
-  if (p.mfma && ddd::train::unrolled_lds_floats(p) * sizeof(float) > 160 * 1024) {
-    p.mfma = 0;
-    p.wl_floats = 0;
-    for (int l = 0; l < p.L; ++l) p.wl_off[l] = -1;
-  }
-  *lds_bytes = ddd::train::unrolled_lds_floats(p) * sizeof(float);
-  if (*lds_bytes > 160 * 1024)
-    return fail(DDD_ERR_UNSUPPORTED, "%s: %zu bytes of LDS needed (> 160 KiB)", who,
-                *lds_bytes);
-  return DDD_OK;
-}
-
-// The configuration checks and kernel parameters of ddd_train_run (train_population.h):
-// train_params into r->q.t for num_time_steps = 0 (r->q.T = 0), train_unrolled_params
-// otherwise, named "training run" (ddd_train_population_run: "training population"); the
-// workspace is theirs plus the coefficient table.
-int train_run_params(const ddd_config* cfg, int batch, int num_time_steps,
-                     ddd::train::RunParams* r, size_t* ws_bytes,
-                     const char* who = "training run") {
-  std::memset(r, 0, sizeof(*r));
-  size_t slabs = 0;
-  int rc;
-  if (num_time_steps == 0) {
-    rc = train_params(cfg, batch, &r->q.t, &r->blocks, &slabs, &r->lds_bytes, who);
-    r->q.HT = r->q.t.H;
-  } else if (num_time_steps < 0) {
-    rc = fail(DDD_ERR_INVALID_ARGUMENT, "num_time_steps = %d (>= 0)", num_time_steps);
-  } else {
-    rc = train_unrolled_params(cfg, batch, num_time_steps, &r->q, &r->blocks, &slabs,
-                               &r->lds_bytes, who);
-  }
-  if (rc) return rc;
-  r->heads = r->q.HT;
-  *ws_bytes = slabs + ddd::train::kCoefTableBytes;   // (slabs: a multiple of 16 bytes)
-  return DDD_OK;
-}
-
-static_assert(ddd::train::kMaxReplicas == DDD_MAX_REPLICAS, "train_population.h / ddd1d.h");
-
-// train_run_params under the name "training population", then the replica count: *ws_bytes
-// is the workspace of ONE replica (ddd_train_run_workspace_bytes)
-int train_population_params(const ddd_config* cfg, int batch, int num_time_steps, int replicas,
-                            ddd::train::RunParams* r, size_t* ws_bytes) {
-  int rc = train_run_params(cfg, batch, num_time_steps, r, ws_bytes, "training population");
-  if (rc) return rc;
-  if (replicas < 1 || replicas > DDD_MAX_REPLICAS)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "replicas = %d out of range [1, %d]", replicas,
-                DDD_MAX_REPLICAS);
-  return DDD_OK;
-}
-
-// The configuration checks and kernel parameters of ddd_eval_metrics (train_metrics.h):
-// train_params (num_time_steps = 0) or train_unrolled_params under the name "evaluation
-// metrics", so exactly the configurations training admits, with its workgroups and LDS
-// plan; then this unit's slab (sums, counts and flag; the pre-activations; the stage
-// states) and the replica count.  *ws_bytes is the workspace of all replicas.
-int eval_metrics_params(const ddd_config* cfg, int rows_evaluated, int num_time_steps,
-                        int replicas, ddd::train::MetricsParams* m, size_t* ws_bytes) {
-  std::memset(m, 0, sizeof(*m));
-  ddd::train::UnrolledParams& q = m->q;
-  ddd::train::TrainParams& p = q.t;
-  size_t slabs = 0, z_floats = 0;
-  int rc;
-  if (num_time_steps == 0) {
-    rc = train_params(cfg, rows_evaluated, &p, &m->blocks, &slabs, &m->lds_bytes,
-                      "evaluation metrics");
-    q.HT = p.H;
-    if (rc == DDD_OK) z_floats = p.slab_stride - (size_t)p.n_slab;
-  } else if (num_time_steps < 0) {
-    rc = fail(DDD_ERR_INVALID_ARGUMENT, "num_time_steps = %d (>= 0)", num_time_steps);
-  } else {
-    rc = train_unrolled_params(cfg, rows_evaluated, num_time_steps, &q, &m->blocks, &slabs,
-                               &m->lds_bytes, "evaluation metrics");
-    if (rc == DDD_OK) z_floats = (size_t)q.st_off - (size_t)p.n_slab;
-  }
-  if (rc) return rc;
-  if (replicas < 1 || replicas > DDD_MAX_REPLICAS)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "replicas = %d out of range [1, %d]", replicas,
-                DDD_MAX_REPLICAS);
-  p.n_slab = ddd::train::metrics_slab_floats(q.HT);
-  q.st_off = (int)((size_t)p.n_slab + z_floats);
-  q.gi_off = 0;
-  p.slab_stride = ((size_t)q.st_off + 2 * (size_t)q.T * p.N + 3) & ~(size_t)3;
-  m->replicas = replicas;
-  *ws_bytes = (size_t)replicas * m->blocks * p.slab_stride * sizeof(float);
-  return DDD_OK;
-}
-
-// What every entry point that runs the training kernels checks first of the dataset it is
-// given, for any of their argument structs (equally named fields): nullspace / bias where
-// the configuration of p projects, and num_rows.
-inline bool projects(const ddd::train::TrainParams& p) {
-  return p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
-}
-
-template <typename Args>
-int check_dataset_args(const Args* a, const ddd::train::TrainParams& p) {
-  if (projects(p) && (!a->nullspace || !a->bias))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "nullspace/bias required for model_target 'coefficients' with "
-                "polynomial_accuracy_order > 0");
-  if (a->num_rows < 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "num_rows = %d", a->num_rows);
-  return DDD_OK;
-}
-
-// ... and last, behind the checks of its own: the workspace of at least ws bytes
-// (ws_bytes_fn names the entry point's workspace function in the message), the `heads`
-// per-head loss constants, finite, into floor / coef_abs / coef_rel, and the dataset and
-// workspace pointers into p.
-template <typename Args>
-int take_dataset_args(const Args* a, ddd::train::TrainParams& p, size_t ws,
-                      const char* ws_bytes_fn, int heads, float* floor, float* coef_abs,
-                      float* coef_rel) {
-  if (a->workspace == nullptr || a->workspace_bytes < ws)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "workspace of %zu bytes given, %s = %zu",
-                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws_bytes_fn, ws);
-  for (int h = 0; h < heads; ++h) {
-    if (!std::isfinite(a->error_floor[h]) || !std::isfinite(a->coef_abs[h]) ||
-        !std::isfinite(a->coef_rel[h]))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_floor / coefficient of head %d", h);
-    floor[h] = a->error_floor[h];
-    coef_abs[h] = a->coef_abs[h];
-    coef_rel[h] = a->coef_rel[h];
-  }
-  p.weights = a->weights;
-  p.nullspace = projects(p) ? a->nullspace : nullptr;
-  p.bias = projects(p) ? a->bias : nullptr;
-  p.y = a->y;
-  p.rows = a->num_rows;
-  p.labels = a->labels;
-  p.baseline = a->baseline;
-  p.ws = static_cast<float*>(a->workspace);
-  return DDD_OK;
-}
-
-// What ddd_train_run and ddd_train_population_run check and copy alike, for Args =
-// ddd_train_run_args / ddd_train_population_args (equally named fields): the arguments
-// into r, whose configuration train_run_params has filled.  ws: the bytes the workspace
-// must have, named ws_bytes_fn in the message; the coefficient table(s) lie table_offset
-// bytes into it.  replicas: 0 for ddd_train_run (learning_rate [num_steps]), otherwise
-// R (learning_rate [R][num_steps]).
-template <typename Args>
-int train_run_args(const Args* a, ddd::train::RunParams& r, size_t ws, size_t table_offset,
-                   int replicas, const char* ws_bytes_fn) {
-  ddd::train::TrainParams& p = r.q.t;
-  if (!a->weights || !a->adam_m || !a->adam_v || !a->y || !a->labels || !a->baseline ||
-      !a->sample_index || !a->learning_rate || !a->head_means_log)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "weights, adam_m, adam_v, y, labels, baseline, sample_index, learning_rate "
-                "and head_means_log must not be NULL");
-  int rc = check_dataset_args(a, p);
-  if (rc) return rc;
-  if (a->num_steps < 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "num_steps = %d (>= 1)", a->num_steps);
-  if (a->first_step < 0)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "first_step = %d (>= 0)", a->first_step);
-  for (int i = 0; i < std::max(replicas, 1); ++i)
-    for (int k = 0; k < a->num_steps; ++k) {
-      const double rate = a->learning_rate[(size_t)i * a->num_steps + k];
-      if (std::isfinite(rate) && rate >= 0.0) continue;
-      if (replicas == 0)
-        return fail(DDD_ERR_INVALID_ARGUMENT, "learning_rate of step %d is %g (finite, >= 0)",
-                    k, rate);
-      return fail(DDD_ERR_INVALID_ARGUMENT,
-                  "learning_rate of replica %d, step %d is %g (finite, >= 0)", i, k, rate);
-    }
-  if (!(a->beta1 >= 0.0 && a->beta1 < 1.0) || !(a->beta2 >= 0.0 && a->beta2 < 1.0))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "beta1 = %g, beta2 = %g outside [0, 1)", a->beta1,
-                a->beta2);
-  if (!(a->epsilon > 0.0) || !std::isfinite(a->epsilon))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "epsilon = %g (> 0)", a->epsilon);
-  if (!(a->error_max >= 0.0) || !std::isfinite(a->error_max))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "error_max = %g (>= 0)", a->error_max);
-  if (a->num_time_steps > 0 && !std::isfinite(a->time_step))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
-  rc = take_dataset_args(a, p, ws, ws_bytes_fn, r.heads, r.floor, r.coef_abs, r.coef_rel);
-  if (rc) return rc;
-  for (int h = 0; h < r.heads; ++h) {
-    if (a->error_max > 0.0 &&
-        (!std::isfinite(a->error_scale_abs[h]) || !std::isfinite(a->error_scale_rel[h])))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite error_scale of head %d", h);
-    r.q.floor[h] = r.floor[h];
-    r.q.coef_abs[h] = r.coef_abs[h];
-    r.q.coef_rel[h] = r.coef_rel[h];
-    if (r.q.T == 0) {   // (heads = H <= kMaxHeads)
-      p.floor[h] = r.floor[h];
-      p.coef_abs[h] = r.coef_abs[h];
-      p.coef_rel[h] = r.coef_rel[h];
-    }
-    r.scale_abs[h] = a->error_scale_abs[h];
-    r.scale_rel[h] = a->error_scale_rel[h];
-  }
-  p.predictions = nullptr;
-  r.q.dt = a->time_step;
-  r.first_step = a->first_step;
-  r.num_steps = a->num_steps;
-  r.learning_rate = a->learning_rate;
-  r.beta1 = a->beta1;
-  r.beta2 = a->beta2;
-  r.epsilon = a->epsilon;
-  r.sample_index = a->sample_index;
-  r.weights = a->weights;
-  r.adam_m = a->adam_m;
-  r.adam_v = a->adam_v;
-  r.head_means_log = a->head_means_log;
-  r.last_grad = a->last_grad;
-  r.error_max = a->error_max;
-  r.coef_table = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + table_offset);
-  return DDD_OK;
-}
-
-// What ddd_train_loss_grad and ddd_train_unrolled_loss_grad check and copy alike, for
-// Args = ddd_train_args / ddd_train_unrolled_args (equally named fields): the argument
-// pointers into p and the `heads` per-head loss constants into floor / coef_abs / coef_rel.
-// ws_bytes_fn names the entry point's workspace function in the message.
-template <typename Args>
-int train_args(const Args* a, ddd::train::TrainParams& p, size_t ws, const char* ws_bytes_fn,
-               int heads, float* floor, float* coef_abs, float* coef_rel) {
-  if (!a->weights || !a->y || !a->labels || !a->baseline || !a->head_means)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "weights, y, labels, baseline and head_means must not be NULL");
-  int rc = check_dataset_args(a, p);
-  if (rc) return rc;
-  if (a->sample_index == nullptr && a->batch > a->num_rows)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "batch = %d > num_rows = %d without a sample_index", a->batch, a->num_rows);
-  if constexpr (std::is_same<Args, ddd_train_unrolled_args>::value)
-    if (!std::isfinite(a->time_step))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
-  rc = take_dataset_args(a, p, ws, ws_bytes_fn, heads, floor, coef_abs, coef_rel);
-  if (rc) return rc;
-  p.sample_index = a->sample_index;
-  p.predictions = a->predictions;
-  p.want_grad = a->grad != nullptr ? 1 : 0;
-  p.grad = a->grad;
-  p.head_means = a->head_means;
-  return DDD_OK;
-}
-
-// What ddd_train_rollout_loss_grad and ddd_train_rollout_run check and copy alike of the
-// windows, for Args = ddd_train_rollout_args / ddd_train_rollout_run_args (equally named
-// fields): save_every, dt, the window tensors, the forcing tables, the projection tables,
-// num_rows and the workspace of at least ws bytes (named ws_bytes_fn in the message), then
-// all of them into q, whose configuration train_rollout_params has filled.
-template <typename Args>
-int take_rollout_windows(const ddd_config* cfg, const Args* a, ddd::train::RolloutParams& q,
-                         size_t ws, const char* ws_bytes_fn) {
-  ddd::train::TrainParams& p = q.t;
-  if (a->save_every < 1 || a->num_steps % a->save_every != 0)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "save_every = %d must be >= 1 and divide num_steps = %d",
-                a->save_every, a->num_steps);
-  if (!(a->dt > 0.0) || !std::isfinite(a->dt))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "dt = %g must be positive and finite", a->dt);
-  if (!a->y0 || !a->targets || !a->step_weights)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "y0, targets and step_weights must not be NULL");
-  const int tables = (a->amplitude != nullptr) + (a->omega != nullptr) + (a->phase != nullptr) +
-                     (a->k_index != nullptr) + (a->spatial_phase != nullptr);
-  if (tables != 0 && tables != 5)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "forcing: amplitude, omega, phase, k_index and spatial_phase must be given "
-                "together (all NULL = unforced)");
-  if (tables == 5 && (a->nparams < 1 || a->n_k < 1))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "forcing: nparams = %d, n_k = %d (>= 1)", a->nparams,
-                a->n_k);
-  int rc = check_dataset_args(a, p);
-  if (rc) return rc;
-  if (a->sample_index == nullptr && a->batch > a->num_rows)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "batch = %d > num_rows = %d without a sample_index", a->batch, a->num_rows);
-  if (a->workspace == nullptr || a->workspace_bytes < ws)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "workspace of %zu bytes given, %s = %zu",
-                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws_bytes_fn, ws);
-  p.nullspace = projects(p) ? a->nullspace : nullptr;
-  p.bias = projects(p) ? a->bias : nullptr;
-  p.y = a->y0;
-  p.rows = a->num_rows;
-  p.ws = static_cast<float*>(a->workspace);
-  q.save_every = a->save_every;
-  q.n_saved = a->num_steps / a->save_every;
-  q.dt = (float)a->dt;
-  q.dt64 = a->dt;
-  q.targets = a->targets;
-  q.step_weights = a->step_weights;
-  q.t0 = a->t0;
-  // KdV and KS: finalize_time_derivative is the identity, the tables are ignored
-  q.forced = tables == 5 && is_forced_family(cfg->equation) ? 1 : 0;
-  if (q.forced) {
-    q.P = a->nparams;
-    q.n_k = a->n_k;
-    q.amplitude = a->amplitude;
-    q.omega = a->omega;
-    q.phase = a->phase;
-    q.k_index = a->k_index;
-    q.spatial_phase = a->spatial_phase;
-  }
-  return DDD_OK;
-}
-
-// train_rollout_params under the name "ddd_train_rollout_run", then the replica count.
-// *slab_bytes: the slabs of ONE replica (ddd_train_rollout_workspace_bytes); *ws_bytes: the
-// whole workspace, R times the slabs and the tail of train_rollout_population.h.
-int train_rollout_run_params(const ddd_config* cfg, int batch, int num_steps, int replicas,
-                             ddd::train::RolloutRunParams* rr, size_t* slab_bytes,
-                             size_t* ws_bytes) {
-  std::memset(rr, 0, sizeof(*rr));
-  int rc = train_rollout_params(cfg, batch, num_steps, &rr->q, &rr->blocks, slab_bytes,
-                                &rr->lds_bytes, "ddd_train_rollout_run");
-  if (rc) return rc;
-  if (replicas < 1 || replicas > DDD_MAX_REPLICAS)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "replicas = %d out of range [1, %d]", replicas,
-                DDD_MAX_REPLICAS);
-  *ws_bytes = (size_t)replicas * *slab_bytes +
-              ddd::train::rollout_run_tail_bytes(rr->q.t.n_weights, num_steps, replicas);
-  return DDD_OK;
 }
 
 }  // namespace
@@ -3199,287 +2680,6 @@ int ddd_polynomial_accuracy_apply(const float* inputs, const float* nullspace,
   return DDD_OK;
 }
 
-size_t ddd_train_workspace_bytes(const ddd_config* cfg, int batch) {
-  ddd::train::TrainParams p;
-  int blocks = 0;
-  size_t ws = 0, lds = 0;
-  if (train_params(cfg, batch, &p, &blocks, &ws, &lds)) return 0;
-  return ws;
-}
-
-int ddd_train_loss_grad(const ddd_config* cfg, const ddd_train_args* a, void* stream) {
-  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
-  if (a->struct_size != (int32_t)sizeof(ddd_train_args))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_train_args.struct_size = %d, library expects %d (ABI mismatch)",
-                a->struct_size, (int)sizeof(ddd_train_args));
-  ddd::train::TrainParams p;
-  int blocks = 0;
-  size_t ws = 0, lds = 0;
-  int rc = train_params(cfg, a->batch, &p, &blocks, &ws, &lds);
-  if (rc) return rc;
-  rc = train_args(a, p, ws, "ddd_train_workspace_bytes", p.H, p.floor, p.coef_abs, p.coef_rel);
-  if (rc) return rc;
-  DDD_HIP(ddd::train::launch_loss_grad(p, blocks, lds, static_cast<hipStream_t>(stream)));
-  return DDD_OK;
-}
-
-size_t ddd_train_unrolled_workspace_bytes(const ddd_config* cfg, int batch, int num_time_steps) {
-  ddd::train::UnrolledParams q;
-  int blocks = 0;
-  size_t ws = 0, lds = 0;
-  if (train_unrolled_params(cfg, batch, num_time_steps, &q, &blocks, &ws, &lds)) return 0;
-  return ws;
-}
-
-int ddd_train_unrolled_loss_grad(const ddd_config* cfg, const ddd_train_unrolled_args* a,
-                                 void* stream) {
-  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
-  if (a->struct_size != (int32_t)sizeof(ddd_train_unrolled_args))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_train_unrolled_args.struct_size = %d, library expects %d (ABI mismatch)",
-                a->struct_size, (int)sizeof(ddd_train_unrolled_args));
-  ddd::train::UnrolledParams q;
-  ddd::train::TrainParams& p = q.t;
-  int blocks = 0;
-  size_t ws = 0, lds = 0;
-  int rc = train_unrolled_params(cfg, a->batch, a->num_time_steps, &q, &blocks, &ws, &lds);
-  if (rc) return rc;
-  rc = train_args(a, p, ws, "ddd_train_unrolled_workspace_bytes", q.HT, q.floor, q.coef_abs,
-                  q.coef_rel);
-  if (rc) return rc;
-  q.dt = a->time_step;
-  DDD_HIP(ddd::train::launch_unrolled_loss_grad(q, blocks, lds, static_cast<hipStream_t>(stream)));
-  return DDD_OK;
-}
-
-size_t ddd_train_rollout_workspace_bytes(const ddd_config* cfg, int batch, int num_steps) {
-  ddd::train::RolloutParams q;
-  int blocks = 0;
-  size_t ws = 0, lds = 0;
-  if (train_rollout_params(cfg, batch, num_steps, &q, &blocks, &ws, &lds)) return 0;
-  return ws;
-}
-
-int ddd_train_rollout_loss_grad(const ddd_config* cfg, const ddd_train_rollout_args* a,
-                                void* stream) {
-  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
-  if (a->struct_size != (int32_t)sizeof(ddd_train_rollout_args))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_train_rollout_args.struct_size = %d, library expects %d (ABI mismatch)",
-                a->struct_size, (int)sizeof(ddd_train_rollout_args));
-  ddd::train::RolloutParams q;
-  ddd::train::TrainParams& p = q.t;
-  int blocks = 0;
-  size_t ws = 0, lds = 0;
-  int rc = train_rollout_params(cfg, a->batch, a->num_steps, &q, &blocks, &ws, &lds);
-  if (rc) return rc;
-  if (!a->weights || !a->step_means)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "weights and step_means must not be NULL");
-  rc = take_rollout_windows(cfg, a, q, ws, "ddd_train_rollout_workspace_bytes");
-  if (rc) return rc;
-  p.weights = a->weights;
-  p.sample_index = a->sample_index;
-  p.want_grad = a->grad != nullptr ? 1 : 0;
-  p.grad = a->grad;
-  p.head_means = a->step_means;
-  q.trajectory = a->trajectory;
-  DDD_HIP(ddd::train::launch_rollout_loss_grad(q, blocks, lds, static_cast<hipStream_t>(stream)));
-  return DDD_OK;
-}
-
-size_t ddd_train_rollout_run_workspace_bytes(const ddd_config* cfg, int batch, int num_steps,
-                                             int replicas) {
-  ddd::train::RolloutRunParams rr;
-  size_t slabs = 0, ws = 0;
-  if (train_rollout_run_params(cfg, batch, num_steps, replicas, &rr, &slabs, &ws)) return 0;
-  return ws;
-}
-
-int ddd_train_rollout_run(const ddd_config* cfg, const ddd_train_rollout_run_args* a,
-                          void* stream) {
-  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
-  if (a->struct_size != (int32_t)sizeof(ddd_train_rollout_run_args))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_train_rollout_run_args.struct_size = %d, library expects %d (ABI mismatch)",
-                a->struct_size, (int)sizeof(ddd_train_rollout_run_args));
-  ddd::train::RolloutRunParams rr;
-  ddd::train::RolloutParams& q = rr.q;
-  ddd::train::TrainParams& p = q.t;
-  size_t slabs = 0, ws = 0;
-  int rc = train_rollout_run_params(cfg, a->batch, a->num_steps, a->replicas, &rr, &slabs, &ws);
-  if (rc) return rc;
-  const int R = a->replicas, K = a->num_opt_steps;
-  if (a->index_per_replica != 0 && a->index_per_replica != 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "index_per_replica = %d (0 or 1)",
-                a->index_per_replica);
-  if (a->forward_only != 0 && a->forward_only != 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "forward_only = %d (0 or 1)", a->forward_only);
-  if (K < 1 || (a->forward_only && K != 1))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "num_opt_steps = %d (>= 1; 1 with forward_only)", K);
-  if (!a->weights || !a->step_means_log)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "weights and step_means_log must not be NULL");
-  if (!a->forward_only) {
-    if (!a->adam_m || !a->adam_v || !a->adam_step || !a->sample_index || !a->learning_rate ||
-        !a->grad_norm_log)
-      return fail(DDD_ERR_INVALID_ARGUMENT,
-                  "adam_m, adam_v, adam_step, sample_index, learning_rate and grad_norm_log "
-                  "must not be NULL");
-    for (int i = 0; i < R; ++i)
-      for (int k = 0; k < K; ++k) {
-        const double rate = a->learning_rate[(size_t)i * K + k];
-        if (!std::isfinite(rate) || rate < 0.0)
-          return fail(DDD_ERR_INVALID_ARGUMENT,
-                      "learning_rate of replica %d, step %d is %g (finite, >= 0)", i, k, rate);
-      }
-    if (!(a->beta1 >= 0.0 && a->beta1 < 1.0) || !(a->beta2 >= 0.0 && a->beta2 < 1.0))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "beta1 = %g, beta2 = %g outside [0, 1)", a->beta1,
-                  a->beta2);
-    if (!(a->epsilon > 0.0) || !std::isfinite(a->epsilon))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "epsilon = %g (> 0)", a->epsilon);
-    if (!(a->clip_norm >= 0.0) || !std::isfinite(a->clip_norm))
-      return fail(DDD_ERR_INVALID_ARGUMENT, "clip_norm = %g (>= 0, finite)", a->clip_norm);
-  }
-  rc = take_rollout_windows(cfg, a, q, ws, "ddd_train_rollout_run_workspace_bytes");
-  if (rc) return rc;
-  p.weights = a->weights;
-  rr.replicas = R;
-  rr.index_per_replica = a->index_per_replica;
-  rr.forward_only = a->forward_only;
-  rr.num_opt_steps = K;
-  rr.learning_rate = a->learning_rate;
-  rr.beta1 = a->beta1;
-  rr.beta2 = a->beta2;
-  rr.epsilon = a->epsilon;
-  rr.clip_norm = a->clip_norm;
-  rr.sample_index = a->sample_index;
-  rr.weights = a->weights;
-  rr.adam_m = a->adam_m;
-  rr.adam_v = a->adam_v;
-  rr.adam_step = a->adam_step;
-  rr.step_means_log = a->step_means_log;
-  rr.grad_norm_log = a->grad_norm_log;
-  rr.last_grad = a->last_grad;
-  // behind the R replicas' slabs: the gradients, the partial sums, the decision records
-  char* tail = static_cast<char*>(a->workspace) + (size_t)R * slabs;
-  rr.grad_buf = reinterpret_cast<float*>(tail);
-  tail += ((size_t)R * p.n_weights * sizeof(float) + 15) & ~(size_t)15;
-  rr.partials = reinterpret_cast<double*>(tail);
-  rr.decisions = reinterpret_cast<ddd::train::RolloutDecision*>(
-      static_cast<char*>(a->workspace) + ws - (size_t)R * sizeof(ddd::train::RolloutDecision));
-  DDD_HIP(ddd::train::launch_train_rollout_run(rr, static_cast<hipStream_t>(stream)));
-  return DDD_OK;
-}
-
-size_t ddd_train_run_workspace_bytes(const ddd_config* cfg, int batch, int num_time_steps) {
-  ddd::train::RunParams r;
-  size_t ws = 0;
-  if (train_run_params(cfg, batch, num_time_steps, &r, &ws)) return 0;
-  return ws;
-}
-
-int ddd_train_run(const ddd_config* cfg, const ddd_train_run_args* a, void* stream) {
-  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
-  if (a->struct_size != (int32_t)sizeof(ddd_train_run_args))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_train_run_args.struct_size = %d, library expects %d (ABI mismatch)",
-                a->struct_size, (int)sizeof(ddd_train_run_args));
-  // the population of one: its slabs, then its coefficient table
-  ddd::train::PopulationParams pp;
-  size_t ws = 0;
-  int rc = train_run_params(cfg, a->batch, a->num_time_steps, &pp.r, &ws);
-  if (rc) return rc;
-  rc = train_run_args(a, pp.r, ws, ws - ddd::train::kCoefTableBytes, 0,
-                      "ddd_train_run_workspace_bytes");
-  if (rc) return rc;
-  pp.replicas = 1;
-  pp.index_per_replica = 0;
-  DDD_HIP(ddd::train::launch_train_population(pp, static_cast<hipStream_t>(stream)));
-  return DDD_OK;
-}
-
-size_t ddd_train_population_workspace_bytes(const ddd_config* cfg, int batch, int num_time_steps,
-                                            int replicas) {
-  ddd::train::RunParams r;
-  size_t ws = 0;
-  if (train_population_params(cfg, batch, num_time_steps, replicas, &r, &ws)) return 0;
-  return (size_t)replicas * ws;
-}
-
-int ddd_train_population_run(const ddd_config* cfg, const ddd_train_population_args* a,
-                             void* stream) {
-  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
-  if (a->struct_size != (int32_t)sizeof(ddd_train_population_args))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_train_population_args.struct_size = %d, library expects %d (ABI mismatch)",
-                a->struct_size, (int)sizeof(ddd_train_population_args));
-  ddd::train::PopulationParams pp;
-  size_t ws = 0;
-  int rc = train_population_params(cfg, a->batch, a->num_time_steps, a->replicas, &pp.r, &ws);
-  if (rc) return rc;
-  if (a->index_per_replica != 0 && a->index_per_replica != 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "index_per_replica = %d (0 or 1)",
-                a->index_per_replica);
-  // the R replicas' slabs, then their R coefficient tables
-  const size_t slabs = ws - ddd::train::kCoefTableBytes;
-  rc = train_run_args(a, pp.r, (size_t)a->replicas * ws, (size_t)a->replicas * slabs,
-                      a->replicas, "ddd_train_population_workspace_bytes");
-  if (rc) return rc;
-  pp.replicas = a->replicas;
-  pp.index_per_replica = a->index_per_replica;
-  DDD_HIP(ddd::train::launch_train_population(pp, static_cast<hipStream_t>(stream)));
-  return DDD_OK;
-}
-
-size_t ddd_eval_metrics_workspace_bytes(const ddd_config* cfg, int rows_evaluated,
-                                        int num_time_steps, int replicas) {
-  ddd::train::MetricsParams m;
-  size_t ws = 0;
-  if (eval_metrics_params(cfg, rows_evaluated, num_time_steps, replicas, &m, &ws)) return 0;
-  return ws;
-}
-
-int ddd_eval_metrics(const ddd_config* cfg, const ddd_eval_metrics_args* a, void* stream) {
-  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
-  if (a->struct_size != (int32_t)sizeof(ddd_eval_metrics_args))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_eval_metrics_args.struct_size = %d, library expects %d (ABI mismatch)",
-                a->struct_size, (int)sizeof(ddd_eval_metrics_args));
-  ddd::train::MetricsParams m;
-  size_t ws = 0;
-  int rc = eval_metrics_params(cfg, a->rows_evaluated, a->num_time_steps, a->replicas, &m, &ws);
-  if (rc) return rc;
-  ddd::train::UnrolledParams& q = m.q;
-  ddd::train::TrainParams& p = q.t;
-  if (a->index_per_replica != 0 && a->index_per_replica != 1)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "index_per_replica = %d (0 or 1)",
-                a->index_per_replica);
-  if (!a->weights || !a->y || !a->labels || !a->baseline || !a->sums || !a->below)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "weights, y, labels, baseline, sums and below must not be NULL");
-  rc = check_dataset_args(a, p);
-  if (rc) return rc;
-  if (a->sample_index == nullptr && a->rows_evaluated > a->num_rows)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "rows_evaluated = %d > num_rows = %d without a sample_index",
-                a->rows_evaluated, a->num_rows);
-  if (a->sample_index == nullptr && a->index_per_replica)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "index_per_replica = 1 without a sample_index");
-  if (a->num_time_steps > 0 && !std::isfinite(a->time_step))
-    return fail(DDD_ERR_INVALID_ARGUMENT, "non-finite time_step");
-  rc = take_dataset_args(a, p, ws, "ddd_eval_metrics_workspace_bytes", q.HT, q.floor, q.coef_abs,
-                         q.coef_rel);
-  if (rc) return rc;
-  p.sample_index = a->sample_index;
-  p.index_stride = a->index_per_replica ? p.batch : 0;
-  p.predictions = a->predictions;
-  q.dt = a->time_step;
-  m.sums = a->sums;
-  m.below = a->below;
-  DDD_HIP(ddd::train::launch_eval_metrics(m, static_cast<hipStream_t>(stream)));
-  return DDD_OK;
-}
-
 static_assert(ddd::rollout::kMaxQuantiles == DDD_ROLLOUT_MAX_QUANTILES &&
                   ddd::rollout::kMaxStopTimes == DDD_ROLLOUT_MAX_STOP_TIMES &&
                   ddd::rollout::kMaxPoints == DDD_ROLLOUT_MAX_POINTS &&
@@ -3487,11 +2687,7 @@ static_assert(ddd::rollout::kMaxQuantiles == DDD_ROLLOUT_MAX_QUANTILES &&
               "rollout_scores.h / ddd1d.h");
 
 int ddd_rollout_reference(const ddd_rollout_reference_args* a, void* stream) {
-  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
-  if (a->struct_size != (int32_t)sizeof(ddd_rollout_reference_args))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_rollout_reference_args.struct_size = %d, library expects %d (ABI mismatch)",
-                a->struct_size, (int)sizeof(ddd_rollout_reference_args));
+  DDD_CHECK_ARGS(a, ddd_rollout_reference_args);
   if (a->num_samples < 1 || a->num_times < 1)
     return fail(DDD_ERR_INVALID_ARGUMENT, "num_samples = %d, num_times = %d (both >= 1)",
                 a->num_samples, a->num_times);
@@ -3553,11 +2749,7 @@ size_t ddd_rollout_scores_workspace_bytes(int replicas, int num_times, int num_s
 }
 
 int ddd_rollout_scores(const ddd_rollout_scores_args* a, void* stream) {
-  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
-  if (a->struct_size != (int32_t)sizeof(ddd_rollout_scores_args))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_rollout_scores_args.struct_size = %d, library expects %d (ABI mismatch)",
-                a->struct_size, (int)sizeof(ddd_rollout_scores_args));
+  DDD_CHECK_ARGS(a, ddd_rollout_scores_args);
   int rc = rollout_sizes(a->replicas, a->num_times, a->num_samples, a->num_quantiles);
   if (rc) return rc;
   if (a->num_points < 1 || a->num_points > DDD_ROLLOUT_MAX_POINTS)
@@ -3613,63 +2805,6 @@ int ddd_rollout_scores(const ddd_rollout_scores_args* a, void* stream) {
   p.mae = a->mae;
   p.survival = a->survival;
   DDD_HIP(ddd::rollout::launch_scores(p, a->times, static_cast<hipStream_t>(stream)));
-  return DDD_OK;
-}
-
-size_t ddd_vjp_workspace_bytes(const ddd_config* cfg, int batch) {
-  ddd::train::TrainParams p;
-  int blocks = 0;
-  size_t ws = 0, lds = 0;
-  if (train_params(cfg, batch, &p, &blocks, &ws, &lds, "ddd_result_vjp")) return 0;
-  return ws;
-}
-
-int ddd_result_vjp(const ddd_config* cfg, const ddd_vjp_args* a, void* stream) {
-  if (a == nullptr) return fail(DDD_ERR_INVALID_ARGUMENT, "args is NULL");
-  if (a->struct_size != (int32_t)sizeof(ddd_vjp_args))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_vjp_args.struct_size = %d, library expects %d (ABI mismatch)",
-                a->struct_size, (int)sizeof(ddd_vjp_args));
-  ddd::train::VjpParams q;
-  std::memset(&q, 0, sizeof(q));
-  ddd::train::TrainParams& p = q.t;
-  int blocks = 0;
-  size_t ws = 0, lds = 0;
-  int rc = train_params(cfg, a->batch, &p, &blocks, &ws, &lds, "ddd_result_vjp");
-  if (rc) return rc;
-  if (!a->weights || !a->y)
-    return fail(DDD_ERR_INVALID_ARGUMENT, "ddd_result_vjp: weights and y must not be NULL");
-  const bool projected = p.target == DDD_TARGET_COEFFICIENTS && p.pao > 0;
-  if (projected && (!a->nullspace || !a->bias))
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_result_vjp: nullspace/bias required for model_target 'coefficients' "
-                "with polynomial_accuracy_order > 0");
-  const bool want_grads = a->grad_y != nullptr || a->grad_weights != nullptr;
-  if (a->cotangent != nullptr && !want_grads)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_result_vjp: a cotangent with grad_y and grad_weights both NULL");
-  if (a->cotangent == nullptr && want_grads)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_result_vjp: grad_y / grad_weights need a cotangent");
-  if (a->cotangent == nullptr && a->predictions == nullptr)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_result_vjp: no cotangent and no predictions: nothing to compute");
-  if (a->workspace == nullptr || a->workspace_bytes < ws)
-    return fail(DDD_ERR_INVALID_ARGUMENT,
-                "ddd_result_vjp: workspace of %zu bytes given, ddd_vjp_workspace_bytes = %zu",
-                a->workspace == nullptr ? (size_t)0 : a->workspace_bytes, ws);
-  p.weights = a->weights;
-  p.nullspace = projected ? a->nullspace : nullptr;
-  p.bias = projected ? a->bias : nullptr;
-  p.y = a->y;
-  p.rows = a->batch;
-  p.predictions = a->predictions;
-  p.ws = static_cast<float*>(a->workspace);
-  p.want_grad = a->grad_weights != nullptr ? 1 : 0;
-  p.grad = a->grad_weights;
-  q.cotangent = a->cotangent;
-  q.grad_y = a->grad_y;
-  DDD_HIP(ddd::train::launch_vjp(q, blocks, lds, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }
 
