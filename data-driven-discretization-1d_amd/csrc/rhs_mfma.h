@@ -499,6 +499,50 @@ __device__ __forceinline__ void activate16(f32x16& acc, int act) {
   }
 }
 
+// relu of one tile of a one-wavefront layer (per-equation resident integrators; activations
+// as in activate16) with the results in registers of their OWN.  In place, the compiler's
+// hazard recognizer -- which cannot see into the asm -- takes the stores behind it for reads
+// of a fresh MFMA result and pads each tile's first store with 18 wait states that the
+// hardware does not need: the stores read what the packed adds wrote.  Early-clobber outputs
+// keep tile 0's results off the accumulators; kReuse (tile 1): the results go where tile 0's
+// went (read-write operands: the statement stays behind tile 0's stores), not onto tile 0's
+// accumulators, which an MFMA wrote a few instructions earlier.
+template <bool kReuse>
+__device__ __forceinline__ void relu_clamp_fresh(f32x16& out, const f32x16& a) {
+  f32x2 y[8];
+#define DDD_PAIR(r) f32x2{a[2 * (r)], a[2 * (r) + 1]}
+  if constexpr (kReuse) {
+    const f32x16& a0 = out;   // (named so that the results keep off tile 0's accumulators)
+#define DDD_PAIR0(r) f32x2{a0[2 * (r)], a0[2 * (r) + 1]}
+    asm("v_pk_add_f32 %0, %8, 0 clamp\n\tv_pk_add_f32 %1, %9, 0 clamp\n\t"
+        "v_pk_add_f32 %2, %10, 0 clamp\n\tv_pk_add_f32 %3, %11, 0 clamp\n\t"
+        "v_pk_add_f32 %4, %12, 0 clamp\n\tv_pk_add_f32 %5, %13, 0 clamp\n\t"
+        "v_pk_add_f32 %6, %14, 0 clamp\n\tv_pk_add_f32 %7, %15, 0 clamp"
+        : "=&v"(y[0]), "=&v"(y[1]), "=&v"(y[2]), "=&v"(y[3]), "=&v"(y[4]), "=&v"(y[5]),
+          "=&v"(y[6]), "=&v"(y[7])
+        : "v"(DDD_PAIR(0)), "v"(DDD_PAIR(1)), "v"(DDD_PAIR(2)), "v"(DDD_PAIR(3)),
+          "v"(DDD_PAIR(4)), "v"(DDD_PAIR(5)), "v"(DDD_PAIR(6)), "v"(DDD_PAIR(7)),
+          "v"(DDD_PAIR0(0)), "v"(DDD_PAIR0(1)), "v"(DDD_PAIR0(2)), "v"(DDD_PAIR0(3)),
+          "v"(DDD_PAIR0(4)), "v"(DDD_PAIR0(5)), "v"(DDD_PAIR0(6)), "v"(DDD_PAIR0(7)));
+#undef DDD_PAIR0
+  } else {
+    asm("v_pk_add_f32 %0, %8, 0 clamp\n\tv_pk_add_f32 %1, %9, 0 clamp\n\t"
+        "v_pk_add_f32 %2, %10, 0 clamp\n\tv_pk_add_f32 %3, %11, 0 clamp\n\t"
+        "v_pk_add_f32 %4, %12, 0 clamp\n\tv_pk_add_f32 %5, %13, 0 clamp\n\t"
+        "v_pk_add_f32 %6, %14, 0 clamp\n\tv_pk_add_f32 %7, %15, 0 clamp"
+        : "=&v"(y[0]), "=&v"(y[1]), "=&v"(y[2]), "=&v"(y[3]), "=&v"(y[4]), "=&v"(y[5]),
+          "=&v"(y[6]), "=&v"(y[7])
+        : "v"(DDD_PAIR(0)), "v"(DDD_PAIR(1)), "v"(DDD_PAIR(2)), "v"(DDD_PAIR(3)),
+          "v"(DDD_PAIR(4)), "v"(DDD_PAIR(5)), "v"(DDD_PAIR(6)), "v"(DDD_PAIR(7)));
+  }
+#undef DDD_PAIR
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    out[2 * r] = y[r][0];
+    out[2 * r + 1] = y[r][1];
+  }
+}
+
 // D of a 32x32 tile -> LDS rows.  Lane l holds position l & 31 and, in register
 // r, out-channel (r & 3) + 8 (r >> 2) + 4 (l >> 5): four ds_write_b128.
 __device__ __forceinline__ void store_tile32(float* out, int trow, int half,
@@ -538,7 +582,8 @@ __device__ __forceinline__ float upper_half_one(float x) {
 // kAddr (specialised one-wave integrators): `bperm` holds the six ds_bpermute
 // byte addresses, resident for the launch; all six permutes are issued before
 // the first MFMA (one LDS-crossbar latency instead of six).
-template <int kWR, bool kShfl, bool kAddr = false>
+// kFreshRelu (one-wavefront per-equation kernels, two tiles): relu_clamp_fresh.
+template <int kWR, bool kShfl, bool kAddr = false, bool kFreshRelu = false>
 __device__ __forceinline__ void input_layer(const DevParams& p, const Lane& ln,
                                             const float* __restrict__ us, float un,
                                             float* __restrict__ out,
@@ -571,9 +616,12 @@ __device__ __forceinline__ void input_layer(const DevParams& p, const Lane& ln,
       b1[t] = kShfl ? __shfl(un, r1, 64) : us[r1];
       b2[t] = kShfl ? __shfl(un, r2, 64) : us[r2];
     }
-    b2[t] = kAddr ? upper_half_one(b2[t]) : (half ? 1.0f : b2[t]);
   }
-  if (kAddr && kShfl) __builtin_amdgcn_sched_group_barrier(0x080, 3 * kT, 0);   // the permutes first
+  // every permute requested before the first wait (nothing crosses: six results in six
+  // registers, one crossbar latency)
+  if (kAddr && kShfl) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int t = 0; t < kT; ++t) b2[t] = kAddr ? upper_half_one(b2[t]) : (half ? 1.0f : b2[t]);
 #pragma unroll
   for (int t = 0; t < kT; ++t) {
 #pragma unroll
@@ -585,6 +633,16 @@ __device__ __forceinline__ void input_layer(const DevParams& p, const Lane& ln,
   for (int t = 0; t < kT; ++t) acc[t] = DDD_MFMA32(w[1], b1[t], acc[t]);
 #pragma unroll
   for (int t = 0; t < kT; ++t) acc[t] = DDD_MFMA32(w[2], b2[t], acc[t]);
+  if constexpr (kFreshRelu) {
+    f32x16 y;
+    relu_clamp_fresh<false>(y, acc[0]);
+    store_tile32_at_bytes(out, st_off, y);
+    __builtin_amdgcn_sched_barrier(0);
+    y = acc[0];
+    relu_clamp_fresh<true>(y, acc[kT - 1]);
+    store_tile32_at_bytes(out, st_off + 32 * kHS * 4, y);
+    return;
+  }
 #pragma unroll
   for (int t = 0; t < kT; ++t) {
     activate16(acc[t], act);
@@ -601,7 +659,8 @@ __device__ __forceinline__ void input_layer(const DevParams& p, const Lane& ln,
 // g + 1 is issued before the four MFMAs of group g (software prefetch).
 // kByteOffsets: `rows` already holds the LDS byte offsets of the operand rows
 // (row * 144 + 64 * half; kept resident by the specialised one-wave integrators).
-template <int kWR, bool kByteOffsets = false, int kPrio = 0>
+// kFreshRelu: as in input_layer.
+template <int kWR, bool kByteOffsets = false, int kPrio = 0, bool kFreshRelu = false>
 __device__ __forceinline__ void hidden_layer(const DevParams& p, const Lane& ln,
                                              const float* __restrict__ in,
                                              float* __restrict__ out,
@@ -658,6 +717,16 @@ __device__ __forceinline__ void hidden_layer(const DevParams& p, const Lane& ln,
 #pragma unroll
   for (int t = 0; t < kT; ++t) {
     acc[t] = DDD_MFMA32(w[80], 1.0f, acc[t]);   // bias row: k = 160 carries b[out]
+  }
+  if constexpr (kFreshRelu) {
+    f32x16 y;
+    relu_clamp_fresh<false>(y, acc[0]);
+    store_tile32_at_bytes(out, st_off, y);
+    __builtin_amdgcn_sched_barrier(0);
+    y = acc[0];
+    relu_clamp_fresh<true>(y, acc[kT - 1]);
+    store_tile32_at_bytes(out, st_off + 32 * kHS * 4, y);
+    return;
   }
 #pragma unroll
   for (int t = 0; t < kT; ++t) {
@@ -1293,12 +1362,38 @@ constexpr int kFin4Ahead = 2;   // operand groups in flight ahead of the MFMAs (
 
 // (TW: the tower -- K taps x C channels: K C / 4 operand groups of four channels,
 // C / 4 per tap row)
-template <int NG, int OG, class TW, int kAcc>
+struct NoTail {
+  static constexpr int kHeadReads = 0, kReads = 0;
+  __device__ __forceinline__ void head() const {}
+  __device__ __forceinline__ void operator()() const {}
+};
+template <int kHeadN, class H, int kN, class F>
+struct Fin4Tail {
+  static constexpr int kHeadReads = kHeadN, kReads = kN;
+  const H& h;
+  const F& f;
+  __device__ __forceinline__ void head() const { h(); }
+  __device__ __forceinline__ void operator()() const { f(); }
+};
+// (Tail: LDS reads of the epilogue, requested with operand group kOperandGroups - kFin4TailAt
+// so that they have landed when the stream ends, Tail::kReads of them; and Tail::kHeadReads
+// reads of forcing phase 2, requested with operand group kFin4HeadAt)
+constexpr int kFin4TailAt = 4, kFin4HeadAt = 1;
+template <int NG, int OG, class TW, int kAcc, class Tail>
 __device__ __forceinline__ void fin4_step(const char* __restrict__ in, const int (&off)[TW::kK],
                                           const float (&w)[fin4_regs_t<TW>(NG)],
-                                          f32x4 (&buf)[kFin4Ahead + 1], f32x4 (&acc)[kAcc]) {
+                                          f32x4 (&buf)[kFin4Ahead + 1], f32x4 (&acc)[kAcc],
+                                          const Tail& tail) {
   constexpr int kNext = OG + kFin4Ahead;
   constexpr int kPerTap = TW::kFinC / 4;
+  if constexpr (Tail::kHeadReads > 0 && OG == kFin4HeadAt) {
+    tail.head();
+    __builtin_amdgcn_sched_group_barrier(0x100, Tail::kHeadReads, 0);
+  }
+  if constexpr (Tail::kReads > 0 && OG == TW::kOperandGroups - kFin4TailAt) {
+    tail();
+    __builtin_amdgcn_sched_group_barrier(0x100, Tail::kReads, 0);
+  }
   if constexpr (kNext < TW::kOperandGroups)
     buf[kNext % (kFin4Ahead + 1)] =
         *reinterpret_cast<const f32x4*>(in + off[kNext / kPerTap] + 16 * (kNext % kPerTap));
@@ -1308,19 +1403,20 @@ __device__ __forceinline__ void fin4_step(const char* __restrict__ in, const int
   __builtin_amdgcn_sched_group_barrier(0x008, 4 * NG, 0);                        // MFMAs
 }
 
-template <int NG, class TW, int kAcc, int... OG>
+template <int NG, class TW, int kAcc, class Tail, int... OG>
 __device__ __forceinline__ void fin4_run(const char* __restrict__ in, const int (&off)[TW::kK],
                                          const float (&w)[fin4_regs_t<TW>(NG)],
                                          f32x4 (&buf)[kFin4Ahead + 1], f32x4 (&acc)[kAcc],
-                                         std::integer_sequence<int, OG...>) {
-  (fin4_step<NG, OG, TW, kAcc>(in, off, w, buf, acc), ...);
+                                         const Tail& tail, std::integer_sequence<int, OG...>) {
+  (fin4_step<NG, OG, TW, kAcc>(in, off, w, buf, acc, tail), ...);
 }
 
 // `off`: LDS byte offsets (row * kHS * 4) of the lane's tap rows.
-template <int NG, class TW = DefaultTower, int kAcc = NG, int kPrio = 0>
+template <int NG, class TW = DefaultTower, int kAcc = NG, int kPrio = 0, class Tail = NoTail>
 __device__ __forceinline__ void final_layer4(const float* __restrict__ in_f,
                                              const float (&w)[fin4_regs_t<TW>(NG)],
-                                             const int (&off)[TW::kK], f32x4 (&acc)[kAcc]) {
+                                             const int (&off)[TW::kK], f32x4 (&acc)[kAcc],
+                                             const Tail& tail = Tail{}) {
   const char* __restrict__ in = reinterpret_cast<const char*>(in_f);
   constexpr int kPerTap = TW::kFinC / 4;
   f32x4 buf[kFin4Ahead + 1];
@@ -1331,7 +1427,8 @@ __device__ __forceinline__ void final_layer4(const float* __restrict__ in_f,
     buf[og] = *reinterpret_cast<const f32x4*>(in + off[og / kPerTap] + 16 * (og % kPerTap));
   __builtin_amdgcn_sched_group_barrier(0x100, kFin4Ahead, 0);
   if (kPrio == 5) __builtin_amdgcn_s_setprio(1);   // (the 8-cycle MFMA stream one level up)
-  fin4_run<NG, TW, kAcc>(in, off, w, buf, acc, std::make_integer_sequence<int, TW::kOperandGroups>{});
+  fin4_run<NG, TW, kAcc>(in, off, w, buf, acc, tail,
+                         std::make_integer_sequence<int, TW::kOperandGroups>{});
   if (kPrio == 5) __builtin_amdgcn_s_setprio(3);
   // bias row: k = K C against a constant 1
   fin4_mfmas<NG, (TW::kFinK - 1) * NG, fin4_regs_t<TW>(NG), kAcc>(
@@ -1470,6 +1567,9 @@ __device__ __forceinline__ WeightShift enter_replica(IntegrateArgs& a, const Pop
 // at the start of the evaluation that uses it.  Inside an evaluation the two
 // phases sit at the input->hidden and hidden->output layer boundaries, where
 // the wavefront otherwise only waits for its activations to land in LDS.
+// (The one-wavefront per-equation kernels shorten that serial stretch further: phase 3 and,
+// in the persistent integrators, the first trip of phase 2 run inside the output layer's
+// MFMA stream -- eval_rhs: kEarlyEpilogue, kStreamSums.)
 // (t: per lane -- the lanes of forcing phase 1 may serve another sample of the group than
 // their own; res.frc_pairs: samples of the group x P)
 template <int kRows, int kWR, bool kWide, class TW>
@@ -1514,6 +1614,42 @@ __device__ __forceinline__ float forcing_phase2(Shared<kRows, kWR, kWide, TW>& s
   return acc;
 }
 
+// forcing_phase2 in three pieces, for the kernels that run its first trip inside the output
+// layer's MFMA stream (eval_rhs: kEarlyEpilogue): the trip's eight reads, its chain, and the
+// rare further trips of runs longer than 8 modes.  The same operations in the same order.
+template <int kRows, int kWR, bool kWide, class TW>
+__device__ __forceinline__ void forcing_phase2_reads(Shared<kRows, kWR, kWide, TW>& sm, const Resident& res,
+                                                     float (&v)[8]) {
+  const float* __restrict__ pm = reinterpret_cast<const float*>(sm.pm) + (res.frc_run & 0xffff);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = pm[2 * i];
+}
+template <bool kMasked>
+__device__ __forceinline__ float forcing_phase2_first(const Resident& res, const float (&v)[8]) {
+  const int cnt = (res.frc_run >> 16) & 0xff;
+  float acc = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    if (kMasked) acc = fmaf(v[i], res.frc_mask[i], acc);
+    else acc = acc + (i < cnt ? v[i] : 0.0f);
+  }
+  return acc;
+}
+template <int kRows, int kWR, bool kWide, class TW>
+__device__ __forceinline__ float forcing_phase2_rest(Shared<kRows, kWR, kWide, TW>& sm, const Resident& res,
+                                                     float acc) {
+  const int cnt = (res.frc_run >> 16) & 0xff;
+  const float* __restrict__ pm = reinterpret_cast<const float*>(sm.pm) + (res.frc_run & 0xffff);
+  for (int m = 8; m < cnt; m += 8) {
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = pm[2 * (m + i)];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc = acc + (m + i < cnt ? v[i] : 0.0f);
+  }
+  return acc;
+}
+
 // (kMasked: forcing_phase2's masked first trip -- the same bits, a third of the
 // instructions; needs Resident::frc_mask, i.e. apply_samples.)
 template <int kRows, int kWR, bool kMasked = false, bool kWide = false, class TW = DefaultTower>
@@ -1535,13 +1671,17 @@ __device__ __forceinline__ float forcing_sums(const DevParams& p, Shared<kRows, 
 // evaluation after this one) at the layer boundaries.
 // ablate / trace: profiling hooks of libddd1d_probe.so (-DDDD_PROBES); every
 // product call site passes the defaults, so they fold away.
-template <int kRows, int kWR, bool kHoist, int kEq, bool kTrace, bool kWide, class TW = DefaultTower>
+// kStreamSums (the persistent integrators, which have the registers for it): the first trip
+// of forcing phase 2 for the next evaluation's time runs inside the output layer's MFMA stream.
+template <int kRows, int kWR, bool kHoist, int kEq, bool kTrace, bool kWide, class TW = DefaultTower,
+          bool kStreamSums = false>
 __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR, kWide, TW>& sm, int batch,
                                           float u, float t, float t_next, Resident& res,
                                           bool fast_forcing, float* derivs_out,
                                           float* coeffs_out, bool prepare_next = true,
                                           int group = -1, int ablate = 0,
-                                          unsigned long long* trace = nullptr) {
+                                          unsigned long long* trace = nullptr,
+                                          std::integral_constant<bool, kStreamSums> = {}) {
 #define DDD_STAMP(i) do { if (kTrace && trace != nullptr && group_tid<kRows, kWR>() == 0) trace[i] = __builtin_amdgcn_s_memtime(); } while (0)
   DDD_STAMP(0);
   // run-time parameters, or compile-time constants when specialised (kEq >= 0)
@@ -1598,6 +1738,11 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
   constexpr bool kKeepOffsets = (kWR == 64 || kSplit || kQuad) && kHoist;
   constexpr bool kKeepRows = kKeepOffsets && kEq >= 0;
   constexpr bool kKeepPatch = kKeepOffsets && !kWide;   // Resident::pch_idx holds 8 columns
+  // one-wavefront per-equation kernels: relu results in fresh registers (relu_clamp_fresh)
+  constexpr bool kFreshRelu = kKeepRows && kOneWave && kWR == 64 && TW::kDefault && !TW::kTile16;
+  // ... and the epilogue's LDS reads (stencil patch, harmonic sums) requested inside the
+  // output layer's stream, forcing phase 3 -- which needs nothing from the net -- right behind it
+  constexpr bool kEarlyEpilogue = kFreshRelu;
   const int tid = opaque(group_tid<kRows, kWR>());
   const Lane ln = make_lane<kRows, kWR>(p, batch, tid, group < 0 ? (int)blockIdx.x : group);
   if (ln.owner) sm.u[ln.row] = u;
@@ -1701,6 +1846,7 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
   float net[kCh];
 #pragma unroll
   for (int c = 0; c < kCh; ++c) net[c] = 0.0f;
+  float total_early = 0.0f;   // (kEarlyEpilogue) forcing phase 3
   if (!fixed) {
     DDD_STAMP(1);
     // issue priority by phase (prio_mode): the VALU phases raised, so that a wavefront's short
@@ -1722,7 +1868,7 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
     } else if constexpr (!TW::kDefault) {
       input_layer_big<TW, kWR, kOneWave>(p, ln, sm.un, un_reg, sm.hA, hid_rows, act);
     } else if (!(ablate & 16)) {
-      input_layer<kWR, kOneWave, kKeepOffsets>(p, ln, sm.un, un_reg, sm.hA, res.w_in, hid_rows,
+      input_layer<kWR, kOneWave, kKeepOffsets, kFreshRelu>(p, ln, sm.un, un_reg, sm.hA, res.w_in, hid_rows,
                                                act, res.in_perm, res.st_off);
     }
     const bool frc_next = forced && fast_forcing && prepare_next && !(ablate & 1);
@@ -1748,7 +1894,7 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
         if constexpr (TW::kTile16) {
           hidden_layer_t16<kPrio>(in, out, res.hid, res.t16_hid_off, res.t16_st_off, act);
         } else {
-          hidden_layer<kWR, kKeepOffsets, kPrio>(p, ln, in, out, res.hid, hid_rows, act, res.st_off);
+          hidden_layer<kWR, kKeepOffsets, kPrio, kFreshRelu>(p, ln, in, out, res.hid, hid_rows, act, res.st_off);
         }
       }
       float* tmp = in; in = out; out = tmp;
@@ -1852,16 +1998,66 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
       // (masked sums where registers allow: the folded kernels; the unfolded
       // non-flux Burgers kernel needs them for the projection)
       constexpr bool kMaskedSums = kKeepRows && spec_folded(kSpec ? kEq : 0);
-      if (frc_next) res.fk_next = forcing_phase2<kRows, kWR, kMaskedSums>(sm, res);
+      constexpr bool kEarlySums = kEarlyEpilogue && kStreamSums && kMaskedSums &&
+                                  spec_forced_family(kSpec ? kEq : 0);
+      if (!kEarlySums && frc_next) res.fk_next = forcing_phase2<kRows, kWR, kMaskedSums>(sm, res);
       group_barrier<kRows, kWR>();
       if constexpr (kSpec) {
         f32x4 acc4[kNG];
+        constexpr bool kSums = kEarlyEpilogue && spec_forced_family(kSpec ? kEq : 0);
+        float4 fk_early[kTrigMax / 4];
+        const auto epilogue_reads = [&]() {
+          if constexpr (kEarlyEpilogue) {
+#pragma unroll
+            for (int g = 0; g < kGW; ++g) pch[g] = (g < nG) ? sm.u[res.pch_idx[g < kGMax ? g : 0]] : 0.0f;
+            if constexpr (kSums) {
+              const float4* __restrict__ fk4 = reinterpret_cast<const float4*>(
+                  reinterpret_cast<const char*>(sm.fk) + res.fk_off);
+#pragma unroll
+              for (int i = 0; i < kTrigMax / 4; ++i) fk_early[i] = fk4[i];
+            }
+          }
+        };
+        constexpr int kTailReads =
+            kEarlyEpilogue ? spec_stencil(kSpec ? kEq : 0) + (kSums ? kTrigMax / 4 : 0) : 0;
+        // forcing phase 2 for the next evaluation's time: its first trip rides in the stream,
+        // whether or not this evaluation prepares the next one (branch-free: a lane without a
+        // run reads the zeroed head of Shared::pm; the sum is taken only under frc_next)
+        float pm_early[8];
+        const auto phase2_reads = [&]() {
+          if constexpr (kEarlySums) forcing_phase2_reads(sm, res, pm_early);
+        };
+        const Fin4Tail<(kEarlySums ? 4 : 0), decltype(phase2_reads), kTailReads, decltype(epilogue_reads)>
+            tail{phase2_reads, epilogue_reads};
         if (!(ablate & 4)) {
           if constexpr (TW::kTile16) final_layer4_t16<kNG, kPrio>(in, wf4, off4, acc4);
-          else final_layer4<kNG, TW, kNG, kPrio>(in, wf4, off4, acc4);
+          else final_layer4<kNG, TW, kNG, kPrio>(in, wf4, off4, acc4, tail);
         } else {
 #pragma unroll
           for (int g4 = 0; g4 < kNG; ++g4) acc4[g4] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+          tail.head();
+          tail();
+        }
+        float sum_next = 0.0f;
+        if constexpr (kEarlySums) {
+          sum_next = forcing_phase2_first<kMaskedSums>(res, pm_early);
+          asm volatile("" : "+v"(sum_next));   // (stays with the stream, as phase 3 below)
+        }
+        if constexpr (kSums) {   // (an unforced model: sums and table are zero, the result unused)
+#pragma unroll
+          for (int i = 0; i < kTrigMax / 4; ++i) {
+            total_early = fmaf(fk_early[i].x, res.trig[i].x, total_early);
+            total_early = fmaf(fk_early[i].y, res.trig[i].y, total_early);
+            total_early = fmaf(fk_early[i].z, res.trig[i].z, total_early);
+            total_early = fmaf(fk_early[i].w, res.trig[i].w, total_early);
+          }
+          // (volatile: the chain stays here, with the stream, and is not sunk to its use
+          // behind the NaN test and the equation of motion; it emits nothing)
+          asm volatile("" : "+v"(total_early));
+          // runs of more than 8 modes: the further trips, behind the stream
+          if constexpr (kEarlySums) {
+            if (frc_next) res.fk_next = forcing_phase2_rest(sm, res, sum_next);
+          }
         }
         // every lane holds its own row's channels: no LDS round trip, no barrier
 #pragma unroll
@@ -1990,7 +2186,7 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
       for (int i = 0; i < kTrigMax / 4; ++i) trig4[i] = tr[i];
     }
   }
-  if (kOneWave) {
+  if (kOneWave && (!kEarlyEpilogue || fixed)) {
 #pragma unroll
     for (int g = 0; g < kGW; ++g)
       pch[g] = (g < nG) ? sm.u[kKeepPatch ? res.pch_idx[g < kGMax ? g : 0]
@@ -2195,7 +2391,9 @@ __device__ __forceinline__ float eval_rhs(const DevParams& p, Shared<kRows, kWR,
     if (!direct_flux) r = -r;        // flux forms: u_t = -d(flux)/dx
   }
   if (forced && !(ablate & 1)) {
-    if (kSpec || fast_forcing) {
+    if (kEarlyEpilogue && !fixed) {
+      r = r + total_early;   // phase 3 ran behind the output layer's stream
+    } else if (kSpec || fast_forcing) {
       // phase 3: combine with this grid point's cos / sin table (both zero
       // padded to 12 entries: no branches)
       const float4* __restrict__ fk4 =
@@ -2812,7 +3010,7 @@ __global__ __launch_bounds__(kRows / kWR * 64, (min_waves<kRows, kWR, TW>())) vo
       const float tn_lane = (float)tn;
       const float f = eval_rhs<kRows, kWR, kHoist, kEq, kTrace>(
           p, sm, a.batch, (float)us, (float)(t + ct.at(s)), tn_lane, res, fast_frc,
-          nullptr, nullptr, true, -1, ablate, tr);
+          nullptr, nullptr, true, -1, ablate, tr, std::true_type{});
       if ((a.sc.b_nonzero >> s) & 1) ynew = ynew + bh.at(s) * (ST)f;
       kprev = f;
     }
