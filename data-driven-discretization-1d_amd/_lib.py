@@ -362,6 +362,49 @@ class DDDVjpArgs(ctypes.Structure):
   ]
 
 
+MAX_TANGENTS = 32   # DDD_MAX_TANGENTS
+
+
+class DDDJvpArgs(ctypes.Structure):
+  """struct ddd_jvp_args."""
+  _fields_ = [
+      ('struct_size', ctypes.c_int32),
+      ('batch', ctypes.c_int32),
+      ('tangents', ctypes.c_int32),
+      ('reserved', ctypes.c_int32),
+      ('weights', ctypes.c_void_p),
+      ('nullspace', ctypes.c_void_p),
+      ('bias', ctypes.c_void_p),
+      ('y', ctypes.c_void_p),
+      ('tangent_y', ctypes.c_void_p),
+      ('tangent_weights', ctypes.c_void_p),
+      ('predictions', ctypes.c_void_p),
+      ('tangents_out', ctypes.c_void_p),
+      ('workspace', ctypes.c_void_p),
+      ('workspace_bytes', ctypes.c_size_t),
+  ]
+
+
+class DDDTangentRolloutArgs(ctypes.Structure):
+  """struct ddd_tangent_rollout_args."""
+  _fields_ = [
+      ('struct_size', ctypes.c_int32),
+      ('batch', ctypes.c_int32),
+      ('tangents', ctypes.c_int32),
+      ('num_steps', ctypes.c_int32),
+      ('dt', ctypes.c_double),
+      ('weights', ctypes.c_void_p),
+      ('nullspace', ctypes.c_void_p),
+      ('bias', ctypes.c_void_p),
+      ('y0', ctypes.c_void_p),
+      ('tangents0', ctypes.c_void_p),
+      ('state_out', ctypes.c_void_p),
+      ('tangents_out', ctypes.c_void_p),
+      ('workspace', ctypes.c_void_p),
+      ('workspace_bytes', ctypes.c_size_t),
+  ]
+
+
 class DDDError(RuntimeError):
   """A libddd1d call returned a non-zero status."""
 
@@ -501,6 +544,14 @@ SIGNATURES = {
                                                    ctypes.c_int]),
     'ddd_result_vjp': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
                                       ctypes.POINTER(DDDVjpArgs), _V]),
+    'ddd_jvp_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(DDDConfig), ctypes.c_int,
+                                                   ctypes.c_int]),
+    'ddd_result_jvp': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
+                                      ctypes.POINTER(DDDJvpArgs), _V]),
+    'ddd_tangent_rollout_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(DDDConfig),
+                                                               ctypes.c_int, ctypes.c_int]),
+    'ddd_tangent_rollout': (ctypes.c_int, [ctypes.POINTER(DDDConfig),
+                                           ctypes.POINTER(DDDTangentRolloutArgs), _V]),
     'ddd_set_kernel': (ctypes.c_int, [_V, ctypes.c_int]),
     'ddd_kernel_name': (ctypes.c_char_p, [_V]),
     'ddd_fma_per_point': (ctypes.c_int64, [_V]),
@@ -1398,6 +1449,119 @@ def result_vjp(cfg, weights, y, cotangent=None, nullspace=None, bias=None,
   args.workspace_bytes = workspace.numel()
   check(lib.ddd_result_vjp(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
   return preds, grad_y, grad_w
+
+
+def _check_tangent_count(tangents):
+  if not 1 <= int(tangents) <= MAX_TANGENTS:
+    raise ValueError('tangents = {} out of range [1, {}]'.format(tangents, MAX_TANGENTS))
+
+
+def result_jvp(cfg, weights, y, tangent_y=None, tangent_weights=None, nullspace=None,
+               bias=None, want_predictions=True, workspace=None):
+  """ddd_result_jvp: (predictions [batch, N, H] or None, tangents [batch, M, N, H]) on the
+  current stream: the Jacobian of one evaluation applied to M directions per sample.
+
+  tangent_y [batch, M, N] (directions of the state) and / or tangent_weights
+  [M, n_weights] (directions of the weights, shared by the batch); with both, the sum of
+  the two contributions.  Everything else as result_vjp, and like there shapes, dtypes and
+  devices are checked before any device work."""
+  lib = load_library()
+  torch = _torch()
+  if not isinstance(y, torch.Tensor) or y.dim() != 2:
+    raise ValueError('y must be a [batch, N] tensor')
+  if tangent_y is None and tangent_weights is None:
+    raise ValueError('tangent_y and tangent_weights are both None')
+  lead = tangent_y if tangent_y is not None else tangent_weights
+  if not isinstance(lead, torch.Tensor) or lead.dim() != (3 if tangent_y is not None else 2):
+    raise ValueError('tangent_y must be a [batch, M, N] tensor, tangent_weights a '
+                     '[M, n_weights] tensor')
+  tangents = int(lead.shape[1] if tangent_y is not None else lead.shape[0])
+  _check_tangent_count(tangents)
+  batch, heads = int(y.shape[0]), cfg.num_derivatives + 1
+  ws_bytes = lib.ddd_jvp_workspace_bytes(ctypes.byref(cfg), batch, tangents)
+  if ws_bytes == 0:
+    check(-1)
+  _check_f32_device('y', y, (batch, cfg.num_points))
+  _check_f32_device('weights', weights, (vjp_num_weights(cfg),))
+  if tangent_y is not None:
+    _check_f32_device('tangent_y', tangent_y, (batch, tangents, cfg.num_points))
+  if tangent_weights is not None:
+    _check_f32_device('tangent_weights', tangent_weights, (tangents, vjp_num_weights(cfg)))
+  for name, tensor in (('nullspace', nullspace), ('bias', bias)):
+    if tensor is not None:
+      _check_f32_device(name, tensor, tuple(tensor.shape))
+  require_gpu()
+  if workspace is None or workspace.numel() < ws_bytes:
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
+  preds = (torch.empty((batch, cfg.num_points, heads), dtype=torch.float32, device=y.device)
+           if want_predictions else None)
+  out = torch.empty((batch, tangents, cfg.num_points, heads), dtype=torch.float32,
+                    device=y.device)
+  args = DDDJvpArgs()
+  args.struct_size = ctypes.sizeof(DDDJvpArgs)
+  args.batch = batch
+  args.tangents = tangents
+  args.weights = weights.data_ptr()
+  args.nullspace = None if nullspace is None else nullspace.data_ptr()
+  args.bias = None if bias is None else bias.data_ptr()
+  args.y = y.data_ptr()
+  args.tangent_y = None if tangent_y is None else tangent_y.data_ptr()
+  args.tangent_weights = None if tangent_weights is None else tangent_weights.data_ptr()
+  args.predictions = None if preds is None else preds.data_ptr()
+  args.tangents_out = out.data_ptr()
+  args.workspace = workspace.data_ptr()
+  args.workspace_bytes = workspace.numel()
+  check(lib.ddd_result_jvp(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
+  return preds, out
+
+
+def tangent_rollout(cfg, weights, y0, tangents0, num_steps, dt, nullspace=None, bias=None,
+                    workspace=None):
+  """ddd_tangent_rollout: (state [batch, N], tangents [batch, M, N]) after num_steps
+  midpoint steps of size dt of y0 [batch, N] and its state tangents tangents0
+  [batch, M, N], in one launch on the current stream.  State tangents only, unforced."""
+  lib = load_library()
+  torch = _torch()
+  if not isinstance(y0, torch.Tensor) or y0.dim() != 2:
+    raise ValueError('y0 must be a [batch, N] tensor')
+  if not isinstance(tangents0, torch.Tensor) or tangents0.dim() != 3:
+    raise ValueError('tangents0 must be a [batch, M, N] tensor')
+  tangents = int(tangents0.shape[1])
+  _check_tangent_count(tangents)
+  if int(num_steps) < 1:
+    raise ValueError('num_steps must be >= 1, got {}'.format(num_steps))
+  batch = int(y0.shape[0])
+  ws_bytes = lib.ddd_tangent_rollout_workspace_bytes(ctypes.byref(cfg), batch, tangents)
+  if ws_bytes == 0:
+    check(-1)
+  _check_f32_device('y0', y0, (batch, cfg.num_points))
+  _check_f32_device('weights', weights, (vjp_num_weights(cfg),))
+  _check_f32_device('tangents0', tangents0, (batch, tangents, cfg.num_points))
+  for name, tensor in (('nullspace', nullspace), ('bias', bias)):
+    if tensor is not None:
+      _check_f32_device(name, tensor, tuple(tensor.shape))
+  require_gpu()
+  if workspace is None or workspace.numel() < ws_bytes:
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=y0.device)
+  state = torch.empty_like(y0)
+  out = torch.empty_like(tangents0)
+  args = DDDTangentRolloutArgs()
+  args.struct_size = ctypes.sizeof(DDDTangentRolloutArgs)
+  args.batch = batch
+  args.tangents = tangents
+  args.num_steps = int(num_steps)
+  args.dt = float(dt)
+  args.weights = weights.data_ptr()
+  args.nullspace = None if nullspace is None else nullspace.data_ptr()
+  args.bias = None if bias is None else bias.data_ptr()
+  args.y0 = y0.data_ptr()
+  args.tangents0 = tangents0.data_ptr()
+  args.state_out = state.data_ptr()
+  args.tangents_out = out.data_ptr()
+  args.workspace = workspace.data_ptr()
+  args.workspace_bytes = workspace.numel()
+  check(lib.ddd_tangent_rollout(ctypes.byref(cfg), ctypes.byref(args), current_stream()))
+  return state, out
 
 
 def load_probe_library():

@@ -1,5 +1,5 @@
 // C ABI of libddd1d.so (include/ddd1d.h), the entry points that take a ddd_config and no
-// ddd_model: training, evaluation metrics and the VJP.  Each checks its arguments, has
+// ddd_model: training, evaluation metrics, the VJP and the tangent-linear model.  Each checks its arguments, has
 // train_plan.h plan the launch, copies the argument pointers into the kernel's parameter
 // struct and calls the launcher of train*.h.  No kernel here.
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@ static_assert(kMaxTimeSteps == DDD_MAX_TIME_STEPS, "train_unrolled.h / ddd1d.h")
 static_assert(kMaxUnrolledHeads == DDD_MAX_UNROLLED_HEADS, "train_unrolled.h / ddd1d.h");
 static_assert(kMaxRolloutSteps == DDD_MAX_ROLLOUT_STEPS, "train_rollout.h / ddd1d.h");
 static_assert(kMaxReplicas == DDD_MAX_REPLICAS, "train_population.h / ddd1d.h");
+static_assert(kMaxTangents == DDD_MAX_TANGENTS, "train.h / ddd1d.h");
 
 namespace {
 
@@ -504,6 +505,83 @@ int ddd_result_vjp(const ddd_config* cfg, const ddd_vjp_args* a, void* stream) {
   q.cotangent = a->cotangent;
   q.grad_y = a->grad_y;
   DDD_HIP(launch_vjp(q, lp.blocks, lp.lds_bytes, static_cast<hipStream_t>(stream)));
+  return DDD_OK;
+}
+
+size_t ddd_jvp_workspace_bytes(const ddd_config* cfg, int batch, int tangents) {
+  JvpParams q;
+  LaunchPlan lp{};
+  return plan_jvp(cfg, batch, tangents, &q, &lp) ? 0 : lp.ws_bytes;
+}
+
+int ddd_result_jvp(const ddd_config* cfg, const ddd_jvp_args* a, void* stream) {
+  DDD_CHECK_ARGS(a, ddd_jvp_args);
+  JvpParams q;
+  TrainParams& p = q.t;
+  LaunchPlan lp{};
+  int rc = plan_jvp(cfg, a->batch, a->tangents, &q, &lp);
+  if (rc) return rc;
+  if (!a->weights || !a->y || !a->tangents_out)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_result_jvp: weights, y and tangents_out must not be NULL");
+  if (projects(p) && (!a->nullspace || !a->bias))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_result_jvp: nullspace/bias required for model_target 'coefficients' "
+                "with polynomial_accuracy_order > 0");
+  if (a->tangent_y == nullptr && a->tangent_weights == nullptr)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_result_jvp: tangent_y and tangent_weights both NULL");
+  rc = take_workspace(a, p, lp.ws_bytes, "ddd_jvp_workspace_bytes", "ddd_result_jvp: ");
+  if (rc) return rc;
+  p.weights = a->weights;
+  p.y = a->y;
+  p.rows = a->batch;
+  p.predictions = a->predictions;
+  q.tangent_y = a->tangent_y;
+  q.tangent_weights = a->tangent_weights;
+  q.tangents_out = a->tangents_out;
+  DDD_HIP(launch_jvp(q, lp.blocks, lp.lds_bytes, static_cast<hipStream_t>(stream)));
+  return DDD_OK;
+}
+
+size_t ddd_tangent_rollout_workspace_bytes(const ddd_config* cfg, int batch, int tangents) {
+  TangentRolloutParams q;
+  LaunchPlan lp{};
+  return plan_tangent_rollout(cfg, batch, tangents, &q, &lp) ? 0 : lp.ws_bytes;
+}
+
+int ddd_tangent_rollout(const ddd_config* cfg, const ddd_tangent_rollout_args* a, void* stream) {
+  DDD_CHECK_ARGS(a, ddd_tangent_rollout_args);
+  TangentRolloutParams q;
+  TrainParams& p = q.t;
+  LaunchPlan lp{};
+  int rc = plan_tangent_rollout(cfg, a->batch, a->tangents, &q, &lp);
+  if (rc) return rc;
+  if (a->num_steps < 1)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "ddd_tangent_rollout: num_steps = %d (>= 1)",
+                a->num_steps);
+  if (!std::isfinite(a->dt))
+    return fail(DDD_ERR_INVALID_ARGUMENT, "ddd_tangent_rollout: dt = %g must be finite", a->dt);
+  if (!a->weights || !a->y0 || !a->tangents0 || !a->state_out || !a->tangents_out)
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_tangent_rollout: weights, y0, tangents0, state_out and tangents_out must "
+                "not be NULL");
+  if (projects(p) && (!a->nullspace || !a->bias))
+    return fail(DDD_ERR_INVALID_ARGUMENT,
+                "ddd_tangent_rollout: nullspace/bias required for model_target 'coefficients' "
+                "with polynomial_accuracy_order > 0");
+  rc = take_workspace(a, p, lp.ws_bytes, "ddd_tangent_rollout_workspace_bytes",
+                      "ddd_tangent_rollout: ");
+  if (rc) return rc;
+  p.weights = a->weights;
+  p.y = a->y0;
+  p.rows = a->batch;
+  q.num_steps = a->num_steps;
+  q.dt = (float)a->dt;
+  q.tangents = a->tangents0;
+  q.state_out = a->state_out;
+  q.tangents_out = a->tangents_out;
+  DDD_HIP(launch_tangent_rollout(q, lp.blocks, lp.lds_bytes, static_cast<hipStream_t>(stream)));
   return DDD_OK;
 }
 

@@ -114,5 +114,38 @@ struct VjpParams {
 // vjp_kernel on `blocks` workgroups, then (want_grad) the slab sum (vjp.hip)
 hipError_t launch_vjp(const VjpParams& q, int blocks, size_t lds_bytes, hipStream_t stream);
 
+// The tangent-linear model (train_tangent.h, jvp.hip): the Jacobian of one model evaluation
+// applied to M tangents per sample (ddd_result_jvp), and M state tangents carried along a
+// midpoint rollout (ddd_tangent_rollout).  Same configurations and LDS plan as training;
+// the slab holds no sums, only scratch: the pre-activations, then at net_off the net output
+// [N][C_out] of the primal pass, which the M tangents of a sample share.
+constexpr int kMaxTangents = 32;
+
+struct JvpParams {
+  TrainParams t;           // configuration, weights, y (rows = batch), predictions, ws
+  int M;                   // tangents per sample
+  int net_off;             // slab offset (floats) of the saved net output
+  const float* tangent_y;        // [batch][M][N] or null
+  const float* tangent_weights;  // [M][n_weights] (shared by the batch) or null
+  float* tangents_out;     // [batch][M][N][H]
+};
+
+struct TangentRolloutParams {
+  TrainParams t;           // configuration, weights, y (the initial states, rows = batch), ws
+  int M;                   // tangents per sample
+  int net_off;             // slab offset (floats) of the saved net output
+  int tan_off;             // slab offset of the tangents [M][N], then the midpoint's [M][N]
+  int num_steps;
+  float dt;
+  const float* tangents;   // [batch][M][N] initial state tangents
+  float* state_out;        // [batch][N]
+  float* tangents_out;     // [batch][M][N]
+};
+
+// jvp_kernel / tangent_rollout_kernel on `blocks` workgroups (jvp.hip); no slab sum
+hipError_t launch_jvp(const JvpParams& q, int blocks, size_t lds_bytes, hipStream_t stream);
+hipError_t launch_tangent_rollout(const TangentRolloutParams& q, int blocks, size_t lds_bytes,
+                                  hipStream_t stream);
+
 }  // namespace train
 }  // namespace ddd

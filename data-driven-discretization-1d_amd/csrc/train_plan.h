@@ -1,4 +1,4 @@
-// The planner of the training, evaluation-metrics and VJP entry points (capi_train.hip):
+// The planner of the training, evaluation-metrics, VJP and tangent entry points (capi_train.hip):
 // which configurations they admit, how a workgroup's slab of the caller's workspace is
 // laid out, and whether the 32 -> 32 layers' kernels are staged in LDS.  Host only: no
 // kernel and no HIP call, so tests/train_plan_harness.hip runs it without a device.  The
@@ -232,6 +232,41 @@ inline int plan_rollout(const ddd_config* cfg, int batch, int T, RolloutParams* 
   q->T = T;
   lay_out_slab(q->t, lp, (size_t)q->t.n_weights + T, 2 * T, T, &q->st_off, &q->gi_off);
   return plan_lds(q->t, lp, 2, who);
+}
+
+inline int check_tangents(int M, const char* who) {
+  if (M < 1 || M > DDD_MAX_TANGENTS)
+    return fail(DDD_ERR_INVALID_ARGUMENT, "%s: tangents = %d out of range [1, %d]", who, M,
+                DDD_MAX_TANGENTS);
+  return DDD_OK;
+}
+
+// ddd_result_jvp: no sums in front; behind the pre-activations the C_out rows of the saved
+// net output.  The tangents are walked one by one through rows the training plan already
+// has, so the LDS plan is training's whatever M is.
+inline int plan_jvp(const ddd_config* cfg, int batch, int M, JvpParams* q, LaunchPlan* lp,
+                    const char* who = "ddd_result_jvp") {
+  std::memset(q, 0, sizeof(*q));
+  int rc = configure(cfg, batch, who, &q->t, lp);
+  if (rc == DDD_OK) rc = check_tangents(M, who);
+  if (rc) return rc;
+  q->M = M;
+  lay_out_slab(q->t, lp, 0, q->t.C_out, 0, &q->net_off, nullptr);
+  return plan_lds(q->t, lp, 0, who);
+}
+
+// ddd_tangent_rollout: behind the saved net output the tangents [M][N] and the midpoint's
+// [M][N]; the state lives in LDS.
+inline int plan_tangent_rollout(const ddd_config* cfg, int batch, int M, TangentRolloutParams* q,
+                                LaunchPlan* lp, const char* who = "ddd_tangent_rollout") {
+  std::memset(q, 0, sizeof(*q));
+  int rc = configure(cfg, batch, who, &q->t, lp);
+  if (rc == DDD_OK) rc = check_tangents(M, who);
+  if (rc) return rc;
+  q->M = M;
+  lay_out_slab(q->t, lp, 0, q->t.C_out + 2 * M, 0, &q->net_off, nullptr);
+  q->tan_off = q->net_off + q->t.C_out * q->t.N;
+  return plan_lds(q->t, lp, 0, who);
 }
 
 // ddd_train_population_run, and ddd_train_run ("training run") as the population of one:

@@ -624,6 +624,75 @@ def evaluate_population(models: Sequence[model_lib.LearnedStencilModel], hparams
   return out
 
 
+def lyapunov_initial_tangents(batch: int, num_exponents: int, num_points: int, seed: int = 0):
+  """The seeded draw lyapunov_exponents starts from: [batch, M, x] float32 on the host,
+  the rows of each sample orthonormal (a float64 Gaussian draw, QR on the host)."""
+  draw = np.random.RandomState(seed).randn(batch, num_points, num_exponents)
+  q, _ = np.linalg.qr(draw)
+  return np.ascontiguousarray(np.swapaxes(q, 1, 2)).astype(np.float32)
+
+
+def lyapunov_exponents(model: model_lib.LearnedStencilModel, y0, num_exponents: int,
+                       num_steps: int, steps_per_orthonormalisation: int,
+                       warmup_steps: int = 0, seed: int = 0, weights=None, tangents=None):
+  """The leading Lyapunov exponents of the learned right-hand side along the midpoint
+  rollout from y0 [batch, x] (float32 device tensor), by Benettin's method: M = num_exponents
+  orthonormal state tangents per sample are carried by ddd_tangent_rollout
+  (model.tangent_time_evolution) for steps_per_orthonormalisation steps of
+  equation.time_step, re-orthonormalised by a batched QR on the device, and log|diag R| is
+  accumulated in float64.  Unforced, like the tangent rollout.
+
+  warmup_steps: steps (in the same stretches, the rest as a shorter one) that align the
+  tangents before anything is accumulated.  tangents: the initial [batch, M, x] instead of
+  the seeded draw (lyapunov_initial_tangents).  num_steps must be a multiple of
+  steps_per_orthonormalisation.
+
+  Returns dict(exponents [batch, M] = log_growth.sum(0) / (num_steps * time_step),
+  log_growth [stretches, batch, M] (float64 device tensors), state [batch, x],
+  tangents [batch, M, x] (float32, orthonormal))."""
+  torch = _lib.require_gpu()
+  stretch = int(steps_per_orthonormalisation)
+  if stretch < 1:
+    raise ValueError('steps_per_orthonormalisation must be >= 1, got {}'.format(stretch))
+  if int(num_steps) < 1 or int(num_steps) % stretch != 0:
+    raise ValueError('num_steps = {} must be a positive multiple of '
+                     'steps_per_orthonormalisation = {}'.format(num_steps, stretch))
+  if int(warmup_steps) < 0:
+    raise ValueError('warmup_steps must be >= 0, got {}'.format(warmup_steps))
+  if not isinstance(y0, torch.Tensor) or y0.dim() != 2:
+    raise ValueError('y0 must be a float32 device tensor [batch, x]')
+  batch, n = y0.shape
+  if not 1 <= int(num_exponents) <= min(_lib.MAX_TANGENTS, n):
+    raise ValueError('num_exponents = {} out of range [1, {}]'.format(
+        num_exponents, min(_lib.MAX_TANGENTS, n)))
+  if tangents is None:
+    tangents = torch.as_tensor(
+        lyapunov_initial_tangents(batch, int(num_exponents), n, seed), device=y0.device)
+  elif tuple(tangents.shape) != (batch, int(num_exponents), n):
+    raise ValueError('tangents must have shape {}'.format((batch, int(num_exponents), n)))
+
+  def advance(state, tangents, steps):
+    state, tangents = model_lib.tangent_time_evolution(state, tangents, model, steps,
+                                                       weights=weights)
+    # (QR in float64: its rounding stays below the float32 rollout's)
+    q, r = torch.linalg.qr(tangents.double().transpose(1, 2))
+    growth = torch.log(torch.diagonal(r, dim1=1, dim2=2).abs())
+    return state, q.transpose(1, 2).float().contiguous(), growth
+
+  state = y0
+  left = int(warmup_steps)
+  while left > 0:
+    state, tangents, _ = advance(state, tangents, min(left, stretch))
+    left -= stretch
+  log_growth = []
+  for _ in range(int(num_steps) // stretch):
+    state, tangents, growth = advance(state, tangents, stretch)
+    log_growth.append(growth)
+  log_growth = torch.stack(log_growth)
+  exponents = log_growth.sum(0) / (int(num_steps) * model.equation.time_step)
+  return dict(exponents=exponents, log_growth=log_growth, state=state, tangents=tangents)
+
+
 def _data(ds, name):
   v = ds.data_vars[name]
   return np.asarray(v[1] if isinstance(v, tuple) else v)

@@ -1009,16 +1009,43 @@ def _result_function():
     import torch
     from torch.autograd.function import once_differentiable
 
-    class ResultVJP(torch.autograd.Function):
-      """Forward: one forward-only call.  Backward: one VJP call, which recomputes
-      the forward pass inside the kernel from the saved y and weights."""
+    class TangentCall(torch.autograd.Function):
+      """The ddd_result_jvp call of ResultVJP.jvp as a function of its own: under
+      torch.func's transforms every tensor inside jvp belongs to the transform's level,
+      and apply() hands forward the tensors below it, whose storage the kernel needs.
+      Not differentiable itself: forward mode is first order, as backward mode is."""
 
       @staticmethod
-      def forward(ctx, y, weights, cfg, nullspace, bias):
+      def forward(y, weights, tangent_y, tangent_w, cfg, nullspace, bias):
+        _, out = _lib.result_jvp(
+            cfg, weights, y,
+            None if tangent_y is None else tangent_y[:, None, :].contiguous(),
+            None if tangent_w is None else tangent_w[None, :].contiguous(),
+            nullspace=nullspace, bias=bias, want_predictions=False)
+        return out[:, 0]
+
+      @staticmethod
+      def setup_context(ctx, inputs, output):
+        ctx.mark_non_differentiable(output)
+
+    class ResultVJP(torch.autograd.Function):
+      """Forward: one forward-only call.  Backward: one VJP call, which recomputes
+      the forward pass inside the kernel from the saved y and weights.  Forward mode
+      (jvp): one ddd_result_jvp call with one tangent per sample, of the state, of the
+      weights or of both.  forward / setup_context are separate so that torch.func's
+      transforms accept the function."""
+
+      @staticmethod
+      def forward(y, weights, cfg, nullspace, bias):
         pred, _, _ = _lib.result_vjp(cfg, weights, y, nullspace=nullspace, bias=bias)
-        ctx.save_for_backward(y, weights)
-        ctx.tables = (cfg, nullspace, bias)
         return pred
+
+      @staticmethod
+      def setup_context(ctx, inputs, output):
+        y, weights, cfg, nullspace, bias = inputs
+        ctx.save_for_backward(y, weights)
+        ctx.save_for_forward(y, weights)
+        ctx.tables = (cfg, nullspace, bias)
 
       @staticmethod
       @once_differentiable
@@ -1030,6 +1057,18 @@ def _result_function():
             want_grad_y=ctx.needs_input_grad[0], want_grad_weights=ctx.needs_input_grad[1])
         return grad_y, grad_w, None, None, None
 
+      @staticmethod
+      def jvp(ctx, tangent_y, tangent_w, *_):
+        y, weights = ctx.saved_tensors
+        cfg, nullspace, bias = ctx.tables
+        if tangent_y is None and tangent_w is None:
+          return torch.zeros((y.shape[0], y.shape[1], cfg.num_derivatives + 1),
+                             dtype=y.dtype, device=y.device)
+        return TangentCall.apply(
+            y.detach(), weights.detach(),
+            None if tangent_y is None else tangent_y.detach(),
+            None if tangent_w is None else tangent_w.detach(), cfg, nullspace, bias)
+
     _RESULT_FUNCTION = ResultVJP
   return _RESULT_FUNCTION
 
@@ -1037,7 +1076,8 @@ def _result_function():
 def differentiable_result(inputs, model: LearnedStencilModel, weights=None):
   """predict_result (model.py:664-697) with torch.autograd: [batch, x, channel] =
   the space derivatives and the equation of motion (no forcing), differentiable with
-  respect to `inputs` and `weights`.
+  respect to `inputs` and `weights`, in reverse mode and in forward mode (torch.func.jvp,
+  torch.autograd.forward_ad).
 
   inputs: float32 device tensor [batch, x].  weights: None (the model's own kernels,
   a constant) or a flat float32 device tensor in the ddd_model_create layout, e.g.
@@ -1073,6 +1113,79 @@ def differentiable_time_evolution(inputs, model: LearnedStencilModel,
     y = y + dt * k2
     states.append(y)
   return torch.stack(states, dim=-1)
+
+
+def _check_tangents(name, tensor, shape_text, ok):
+  import torch
+  if (not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float32 or
+      not tensor.is_cuda or not tensor.is_contiguous() or not ok(tensor)):
+    raise ValueError('{} must be a contiguous float32 device tensor {}'.format(
+        name, shape_text))
+  count = tensor.shape[1] if tensor.dim() == 3 else tensor.shape[0]
+  if not 1 <= count <= _lib.MAX_TANGENTS:
+    raise ValueError('{}: {} tangents, 1 .. {} are supported'.format(
+        name, count, _lib.MAX_TANGENTS))
+
+
+def tangent_result(inputs, tangents, model: LearnedStencilModel, weights=None,
+                   weight_tangents=None):
+  """Forward mode beside differentiable_result's reverse mode (ddd_result_jvp,
+  csrc/jvp.hip): (predictions [batch, x, channel], tangents_out [batch, M, x, channel]),
+  the Jacobian of predict_result (no forcing) applied to M directions per sample.
+
+  tangents: [batch, M, x] directions of the state, or None.  weight_tangents:
+  [M, n_weights] directions of the weights (ddd_model_create layout), shared by the
+  batch, or None.  At least one of the two; with both, the sum of the two contributions.
+  M is at most _lib.MAX_TANGENTS.  No autograd graph is recorded."""
+  cfg = _vjp_setup(model)
+  weights = _check_state_and_weights(inputs, model, weights)
+  if tangents is None and weight_tangents is None:
+    raise ValueError('tangents and weight_tangents are both None')
+  batch, n = inputs.shape
+  if tangents is not None:
+    _check_tangents('tangents', tangents, '[{}, M, {}]'.format(batch, n),
+                    lambda t: t.dim() == 3 and t.shape[0] == batch and t.shape[2] == n)
+  if weight_tangents is not None:
+    size = weights.shape[0]
+    _check_tangents('weight_tangents', weight_tangents, '[M, {}]'.format(size),
+                    lambda t: t.dim() == 2 and t.shape[1] == size)
+    if tangents is not None and weight_tangents.shape[0] != tangents.shape[1]:
+      raise ValueError('tangents and weight_tangents differ in M: {} and {}'.format(
+          tangents.shape[1], weight_tangents.shape[0]))
+  nullspace, bias = _vjp_tables(model)
+  return _lib.result_jvp(cfg, weights.detach(), inputs.detach(), tangents, weight_tangents,
+                         nullspace=nullspace, bias=bias)
+
+
+def tangent_time_evolution(inputs, tangents, model: LearnedStencilModel, num_time_steps,
+                           weights=None, fused=True):
+  """The state and M state tangents per sample after num_time_steps midpoint steps of
+  equation.time_step: (state [batch, x], tangents [batch, M, x]).  State tangents only,
+  and unforced, like differentiable_time_evolution; nothing per step is kept.
+
+  fused=True: one launch (ddd_tangent_rollout).  fused=False: the same recurrence
+  composed from tangent_result calls in torch."""
+  cfg = _vjp_setup(model)
+  if num_time_steps is None or int(num_time_steps) < 1:
+    raise ValueError('num_time_steps must be >= 1, got {}'.format(num_time_steps))
+  weights = _check_state_and_weights(inputs, model, weights)
+  batch, n = inputs.shape
+  _check_tangents('tangents', tangents, '[{}, M, {}]'.format(batch, n),
+                  lambda t: t.dim() == 3 and t.shape[0] == batch and t.shape[2] == n)
+  dt = model.equation.time_step
+  nullspace, bias = _vjp_tables(model)
+  if fused:
+    return _lib.tangent_rollout(cfg, weights.detach(), inputs.detach(), tangents,
+                                int(num_time_steps), dt, nullspace=nullspace, bias=bias)
+  y, t = inputs.detach(), tangents
+  for _ in range(int(num_time_steps)):
+    pred, dpred = tangent_result(y, t, model, weights)
+    y_mid = (y + (0.5 * dt) * pred[..., -1]).contiguous()
+    t_mid = (t + (0.5 * dt) * dpred[..., -1]).contiguous()
+    pred, dpred = tangent_result(y_mid, t_mid, model, weights)
+    y = (y + dt * pred[..., -1]).contiguous()
+    t = (t + dt * dpred[..., -1]).contiguous()
+  return y, t
 
 
 # ---------------------------------------------------------------------------

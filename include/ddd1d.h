@@ -1090,6 +1090,72 @@ DDD_API size_t ddd_vjp_workspace_bytes(const ddd_config* cfg, int batch);
  * recomputed inside the call; nothing is kept between calls. */
 DDD_API int ddd_result_vjp(const ddd_config* cfg, const ddd_vjp_args* args, void* stream);
 
+/* ---- tangent-linear model ---------------------------------------------------
+ * Forward mode beside ddd_result_vjp's reverse mode: the Jacobian of one model
+ * evaluation applied to vectors, and state perturbations carried along a
+ * rollout (stability of the linearised scheme, Lyapunov exponents).  Stateless,
+ * the weights a device vector in the ddd_model_create layout; exactly the
+ * configurations ddd_result_vjp supports, the others return DDD_ERR_UNSUPPORTED
+ * before any device work.  No forcing: the forcing term depends neither on the
+ * state nor on the weights.  Deterministic: every output is per sample, no
+ * atomics, no cross-sample sum, so equal inputs give bit-identical outputs. */
+#define DDD_MAX_TANGENTS 32
+
+typedef struct ddd_jvp_args {
+  int32_t struct_size;   /* = sizeof(ddd_jvp_args), checked */
+  int32_t batch;         /* rows of y */
+  int32_t tangents;      /* M, tangents per sample, in [1, DDD_MAX_TANGENTS] */
+  int32_t reserved;      /* 0 */
+  const float* weights;  /* conv weights (ddd_model_create layout, as ddd_train_args) */
+  const float* nullspace; /* as ddd_train_args */
+  const float* bias;     /* as ddd_train_args */
+  const float* y;        /* [batch][N] */
+  const float* tangent_y; /* [batch][M][N] directions of the state, or NULL */
+  const float* tangent_weights; /* [M][n_weights] directions of the weights, shared by the
+                          * batch, or NULL */
+  float* predictions;    /* out [batch][N][H] or NULL (bit for bit ddd_result_vjp's) */
+  float* tangents_out;   /* out [batch][M][N][H] */
+  void* workspace;       /* ddd_jvp_workspace_bytes(cfg, batch, tangents) bytes */
+  size_t workspace_bytes;
+} ddd_jvp_args;
+
+/* Bytes of the caller-allocated workspace of ddd_result_jvp (per-workgroup scratch);
+ * 0 on error. */
+DDD_API size_t ddd_jvp_workspace_bytes(const ddd_config* cfg, int batch, int tangents);
+/* tangents_out[b][j] = d predictions / d y (y[b]) tangent_y[b][j]
+ *                    + d predictions / d weights (y[b]) tangent_weights[j].
+ * At least one of tangent_y and tangent_weights; with both, the sum of the two
+ * contributions.  The space-derivative channels of model_target 'time_derivative'
+ * are zero, and so is their tangent.  The forward pass runs once per sample. */
+DDD_API int ddd_result_jvp(const ddd_config* cfg, const ddd_jvp_args* args, void* stream);
+
+typedef struct ddd_tangent_rollout_args {
+  int32_t struct_size;   /* = sizeof(ddd_tangent_rollout_args), checked */
+  int32_t batch;         /* rows of y0 */
+  int32_t tangents;      /* M, tangents per sample, in [1, DDD_MAX_TANGENTS] */
+  int32_t num_steps;     /* >= 1 */
+  double dt;             /* step size */
+  const float* weights;  /* as ddd_jvp_args */
+  const float* nullspace;
+  const float* bias;
+  const float* y0;       /* [batch][N] */
+  const float* tangents0; /* [batch][M][N] state tangents at y0 */
+  float* state_out;      /* out [batch][N] the state after num_steps steps */
+  float* tangents_out;   /* out [batch][M][N] the tangents after num_steps steps */
+  void* workspace;       /* ddd_tangent_rollout_workspace_bytes(cfg, batch, tangents) bytes */
+  size_t workspace_bytes;
+} ddd_tangent_rollout_args;
+
+DDD_API size_t ddd_tangent_rollout_workspace_bytes(const ddd_config* cfg, int batch,
+                                                   int tangents);
+/* num_steps explicit-midpoint steps of the state and of its M tangents in one launch:
+ *   k1 = f(y), dk1 = J(y) t;  y_m = y + dt/2 k1, t_m = t + dt/2 dk1;
+ *   k2 = f(y_m), dk2 = J(y_m) t_m;  y += dt k2, t += dt dk2.
+ * State tangents only, and unforced (like model.differentiable_time_evolution).
+ * Nothing per step is kept. */
+DDD_API int ddd_tangent_rollout(const ddd_config* cfg, const ddd_tangent_rollout_args* args,
+                                void* stream);
+
 /* ---- introspection -------------------------------------------------------*/
 DDD_API int ddd_set_kernel(ddd_model* model, int kernel_kind);
 /* "mfma_f32_r64", "mfma_f32_r64w32", "mfma_f32_r64w16" (small ensembles: every 64-row group
